@@ -14,11 +14,17 @@ Reservation halves), shipped (the reference's shipped profile, config/manager/sc
 LoadAware + NodeNUMAResource + DeviceShare + Reservation + ElasticQuota on 256-cpu NUMA nodes with 8 GPUs), stock / stockz
 (the k8s v1.24 default profile + LoadAware with hostname / also zone-keyed PodTopologySpread and InterPodAffinity).
 
+A plain run sets up, warms up, times the `--steps` steps and prints the headline line (metric, value, ms_per_step, the
+workload's configuration, placed pods and device rounds).  `--dump-outputs DIR` also writes what the last timed step
+returned to its caller (kg_results_fetch of that step's pods) as DIR/node.npy and DIR/score.npy (float64, one entry
+per pod of the step).  The queue is seeded, so two builds run with the same arguments can be compared output for output.
+Everything below runs only with `--full`, which adds its results to the same line.
+
 Single-pod calls (the drop-in's scheduleOne, framework_extender_factory.go:156-185): after the timed region
 `--single-pod-calls` more queued pods are scheduled one kg_pods_schedule_staged call each, and the same number through
 kg_pods_schedule (host pod in, host decision out); p50 / p99 microseconds per call are reported.
 
-After the timed region: (1) `--profile-pods` more queued pods are scheduled with live kernel timing (HIP events
+After the timed region (`--full`): (1) `--profile-pods` more queued pods are scheduled with live kernel timing (HIP events
 bracketing every launch on its own stream, kg_profile_enable) — the roofline's kernel time; (2) the first
 `--check` placements are compared with the oracle (bit-exact), and (r6) for C3 every timed placement and total
 with the committed oracle fixture of the whole queue (tests/golden/c3_queue.npz); (3) the CPU baseline (the oracle, the same
@@ -67,8 +73,14 @@ WORKLOADS = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 10; c1: 1, its whole 5k-pod queue)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the live kernel timing and roofline, the single-pod calls, the "
+                         "PCIe-inclusive step, the oracle / fixture checks and the CPU baseline (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (node index and total score per pod) as DIR/node.npy and "
+                         "DIR/score.npy, float64")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
     ap.add_argument("--nodes", type=int, default=None)
     ap.add_argument("--pods-per-step", type=int, default=None)
@@ -265,6 +277,16 @@ def fixture_check(wl, n_nodes, pods, node_idx, score, total):
     return ok, total, f"tests/golden/{name} ({meta['oracle']}, {meta['pods']} pods)", "score" in z.files
 
 
+def dump_outputs(path, node_idx, score):
+    """--dump-outputs: the last timed step's kg_results_fetch arrays (int32 node index, -1 = unschedulable; int64 total
+    score), every pod of the step, as float64 (both are exact in it)."""
+    os.makedirs(path, exist_ok=True)
+    if len(score) and int(np.abs(score).max()) >= 2 ** 53:
+        raise SystemExit("--dump-outputs: a total score does not fit float64 exactly")
+    np.save(os.path.join(path, "node.npy"), node_idx.astype(np.float64))
+    np.save(os.path.join(path, "score.npy"), score.astype(np.float64))
+
+
 def workload_profile(wl):
     """(profile, LoadAwareSchedulingArgs) of a workload (None = the engine defaults)."""
     from koordinator_amd import framework as F
@@ -339,14 +361,18 @@ def main():
     args.batch = args.batch or b0
     args.pods_per_wave = args.pods_per_wave or ppw0
     args.check = check0 if args.check is None else args.check
-    if wl == "c1" and args.steps == 10:
-        args.steps = 1  # the whole 5k-pod queue of config 1
+    if args.steps is None:
+        args.steps = 1 if wl == "c1" else 10  # c1: the whole 5k-pod queue of config 1
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     profile, la = workload_profile(wl)
     cfg = framework.build_config(batch_pods=args.batch, pods_per_wave=args.pods_per_wave, device_id=d.local_rank,
                                  profile=profile, pipeline_depth=args.depth, la=la, multi_rank=args.multi_rank)
     work = Work(wl, args.nodes, cfg)
     cluster = work.cluster
     total = args.steps * args.pods_per_step
+    # the pods --full schedules after the timed region are queued in a plain run too: only the C3 / C4 / shipped
+    # generators are prefix-stable, so the timed pods are the same with and without --full
     n_prof = args.profile_pods if args.profile_pods is not None else min(args.pods_per_step, 20_000)
     n_single = args.single_pod_calls if d.world == 1 else 0
     pods = work.make_pods(total + n_prof + n_single, seed=work.seed + 1)
@@ -393,6 +419,14 @@ def main():
     elapsed = d.max(t1 - t0)
     node_idx, score_tot = e.fetch(0, total)
     placed = int((node_idx >= 0).sum())
+    if args.dump_outputs and d.rank == 0:
+        dump_outputs(args.dump_outputs, *e.fetch(total - args.pods_per_step, args.pods_per_step))
+    if not args.full:  # the plain run: the headline of the timed steps, nothing else measured or checked
+        if d.rank == 0:
+            print(json.dumps(headline(args, d, work, total, elapsed, e.ranks, placed, rounds)), flush=True)
+        e.close()
+        d.close()
+        return
 
     # live kernel timing on the real pipelined runner, continuing the same queue (outside the timed region)
     live = {}
@@ -425,7 +459,7 @@ def main():
                        "note": "kg_pods_schedule_staged(count=1) continuing the staged queue after the timed region; "
                                "kg_pods_schedule(1 host pod) on a fresh engine: decode + upload + schedule + result"})
     # isolated replays of one round's kernels (warm caches, no concurrency) for comparison
-    rsv_path = wl in ("c5r", "c5", "shipped", "stock", "stockz")
+    rsv_path = wl in RSV_PATH
     names = (("rsv_eval", "rsv_select") if rsv_path else
              ("eval_round", "merge_round", "resolve_round") + (("ds_max_round", "ds_norm_reduce") if wl == "c5ds" else ()))
     isolated = {name: e.bench_kernel(which, args.kernel_iters) for which, name in enumerate(names)}
@@ -537,85 +571,9 @@ def main():
                                         if active_s > 0 else None),
                   "note": "resolver_share = in-kernel active time / wall time of the timed steps (the serial chain "
                           "sets the period when it is near 1); eval_stream_share = (eval + merge) / (depth x period)"}
-    if d.world == 1:
-        parallelism = "1 GPU"
-    elif replica_ranks > 1:
-        parallelism = ("replicas x%d (multi_rank %s: the sharding model of DESIGN §6 predicts no gain at %d nodes, so "
-                       "every rank is an independent scheduler over its own %d-pod queue on its own full table, no "
-                       "exchange; value = the pods all ranks scheduled per second)"
-                       % (d.world, args.multi_rank, cluster.n, total))
-    elif wl in ("stock", "stockz"):
-        parallelism = ("replicas x%d (per-pod exact pass: every rank evaluates its full replica, no exchange)" % d.world)
-    elif rsv_path:
-        parallelism = ("node-sharded exact rounds x%d (replicated table; per round an RCCL all-gather of the pod "
-                       "statistics and of the merged records)" % shard_ranks)
-    else:
-        parallelism = "node-sharded x%d (replicated table, RCCL all-gather)" % shard_ranks
     if d.rank == 0:
-        pods_s = total * (d.world if independent else 1) / elapsed
-        desc = {
-            "c1": "C1 cluster: %d nodes, %d-pod FIFO queue, NodeResourcesFit+LoadAwareScheduling, %d pods per step",
-            "c2": "C2 cluster: %d nodes, %d-pod FIFO queue, NodeResourcesFit+LoadAwareScheduling, %d pods per step",
-            "shipped": "shipped profile (config/manager/scheduler-config.yaml:66-117): %d 2-socket 256-cpu NUMA nodes x "
-                       "8 GPUs (30%% with 1-4 cpu/memory reservations), %d-pod FIFO queue (70%% cpuset LSR/LSE, 30%% "
-                       "GPU-share, 20%% reservation-owned, 80%% in 16 ElasticQuota groups), NodeResourcesFit+"
-                       "LoadAwareScheduling+NodeNUMAResource+DeviceShare+Reservation (w 1/1/1/1/5000)+ElasticQuota, "
-                       "batched exact rounds of 32 pods, %d pods per step",
-            "c3": "C3 cluster: %d nodes, %d-pod FIFO queue, NodeResourcesFit+LoadAwareScheduling, %d pods per step",
-            "c4": "C4 cluster: %d 2-socket 256-cpu nodes (node count: builder's choice, BASELINE names none), "
-                  "%d-pod FIFO queue (70%% cpuset LSR/LSE), NodeResourcesFit+LoadAwareScheduling+NodeNUMAResource, "
-                  "%d pods per step",
-            "c5ds": "C5 (DeviceShare part): %d nodes x 8 GPUs, %d-pod FIFO queue (30%% GPU-share), "
-                    "NodeResourcesFit+LoadAwareScheduling+DeviceShare, %d pods per step",
-            "c5": "C5 (one profile): %d nodes x 8 GPUs (30%% with 1-4 cpu/memory reservations, 64 owner groups), "
-                  "%d-pod FIFO queue (30%% GPU-share, 20%% reservation-owned, 80%% in 16 ElasticQuota groups), "
-                  "NodeResourcesFit+LoadAwareScheduling+Reservation (w 5000)+DeviceShare+ElasticQuota admission, "
-                  "batched exact rounds of 32 pods, %d pods per step",
-            "c5r": "C5 (Reservation part): %d nodes (30%% with 1-4 reservations), %d-pod FIFO queue (20%% "
-                   "reservation-owned), NodeResourcesFit+LoadAwareScheduling+Reservation (w 5000), batched exact "
-                   "rounds of 32 pods, %d pods per step",
-            "stock": "k8s v1.24 default profile + LoadAware: %d nodes (labels, NoSchedule / PreferNoSchedule taints), "
-                     "%d-pod FIFO queue of 8 deployments in 4 teams (40%% DoNotSchedule / 50%% ScheduleAnyway hostname "
-                     "spread, 15%% required anti-affinity, 10%% required affinity, 30%% preferred terms), NodeResourcesFit"
-                     "+LoadAware+TaintToleration+NodeAffinity+BalancedAllocation+PodTopologySpread(w2)+InterPodAffinity, "
-                     "one pod per exact pass, %d pods per step",
-            "stockz": "k8s v1.24 default profile + LoadAware with zone keys: %d nodes in 4 zones (5%% without the zone "
-                      "label), %d-pod FIFO queue of 8 deployments in 4 teams (hostname and zone spread constraints in "
-                      "random order; a third of required anti-affinity, half of required affinity and half of "
-                      "preferred terms zone-keyed), the stock profile's plugins and weights, one pod per exact pass, "
-                      "%d pods per step",
-        }[wl] % (cluster.n, total, args.pods_per_step)
-        out = {
-            "metric": {"c3": "pods scheduled/sec at 100k nodes (node-evals/sec alongside)",
-                       "c1": "pods scheduled/sec, config 1 (500 nodes; node-evals/sec alongside)",
-                       "c2": "pods scheduled/sec, config 2 (10k nodes; node-evals/sec alongside)",
-                       "shipped": "pods scheduled/sec, the shipped koord-scheduler profile (node-evals/sec alongside)",
-                       "c4": "pods scheduled/sec, NodeNUMAResource cpuset/NUMA profile (node-evals/sec alongside)",
-                       "c5ds": "pods scheduled/sec, DeviceShare GPU-share profile (node-evals/sec alongside)",
-                       "c5r": "pods scheduled/sec, Reservation profile (node-evals/sec alongside)",
-                       "c5": "pods scheduled/sec, Reservation+DeviceShare+ElasticQuota profile (node-evals/sec "
-                             "alongside)",
-                       "stock": "pods scheduled/sec, default plugins + hostname PodTopologySpread / InterPodAffinity "
-                                "(node-evals/sec alongside)",
-                       "stockz": "pods scheduled/sec, default plugins + hostname / zone PodTopologySpread / "
-                                 "InterPodAffinity (node-evals/sec alongside)"}[wl],
-            "value": pods_s,
-            "unit": "pods/s",
-            "n_gpus": d.world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak" if independent else "strong",
-            "vs_baseline": None,
-            "dtype": "int64",
-            "data": "synthetic (SURVEY §8d generator, seed %d)" % work.seed,
-            "config": {"workload": desc, "nodes": cluster.n, "pods": total, "batch_pods": args.batch,
-                       "pods_per_wave": args.pods_per_wave, "pipeline_depth": args.depth or "default",
-                       "parallelism": parallelism},
-            "node_evals_per_sec": pods_s * cluster.n,
-            "placed": placed,
-            "device_rounds": rounds,
+        out = headline(args, d, work, total, elapsed, e.ranks, placed, rounds)
+        out.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "kernel_ms": dom_ms, "algo_bytes_per_launch": algo,
@@ -636,17 +594,106 @@ def main():
             "pcie_inclusive_pods_per_sec": pcie,
             "single_pod_call": single,
             # (r6) the whole timed queue against the committed oracle fixture when one covers it, and the live oracle
-            # on the first --check pods (the fixture's own check on this box)
+            # on the first --check pods (the fixture's own check on this host)
             "oracle_check": (None if check is None and fx is None else
                              (check is not False) and (fx is None or fx[0])),
             "oracle_check_pods": max(min(args.check, total) if args.check else 0, fx[1] if fx else 0),
             "oracle_check_live_pods": min(args.check, total) if args.check else 0,
             "oracle_check_fixture": ({"ok": fx[0], "pods": fx[1], "placements_and_totals": fx[3], "source": fx[2]}
                                      if fx else None),
-        }
+        })
         print(json.dumps(out), flush=True)
     e.close()
     d.close()
+
+
+RSV_PATH = ("c5r", "c5", "shipped", "stock", "stockz")  # workloads that run the exact wide pass (rsv_eval / xr_eval)
+
+
+def headline(args, d, work, total, elapsed, ranks, placed, rounds):
+    """The result line of the timed steps alone: what a plain run prints, and what --full adds its results to."""
+    wl, n = work.name, work.cluster.n
+    shard_ranks, replica_ranks = ranks
+    independent = d.world > 1 and replica_ranks > 1
+    if d.world == 1:
+        parallelism = "1 GPU"
+    elif replica_ranks > 1:
+        parallelism = ("replicas x%d (multi_rank %s: the sharding model of DESIGN §6 predicts no gain at %d nodes, so "
+                       "every rank is an independent scheduler over its own %d-pod queue on its own full table, no "
+                       "exchange; value = the pods all ranks scheduled per second)"
+                       % (d.world, args.multi_rank, n, total))
+    elif wl in ("stock", "stockz"):
+        parallelism = ("replicas x%d (per-pod exact pass: every rank evaluates its full replica, no exchange)" % d.world)
+    elif wl in RSV_PATH:
+        parallelism = ("node-sharded exact rounds x%d (replicated table; per round an RCCL all-gather of the pod "
+                       "statistics and of the merged records)" % shard_ranks)
+    else:
+        parallelism = "node-sharded x%d (replicated table, RCCL all-gather)" % shard_ranks
+    pods_s = total * (d.world if independent else 1) / elapsed
+    desc = {
+        "c1": "C1 cluster: %d nodes, %d-pod FIFO queue, NodeResourcesFit+LoadAwareScheduling, %d pods per step",
+        "c2": "C2 cluster: %d nodes, %d-pod FIFO queue, NodeResourcesFit+LoadAwareScheduling, %d pods per step",
+        "shipped": "shipped profile (config/manager/scheduler-config.yaml:66-117): %d 2-socket 256-cpu NUMA nodes x "
+                   "8 GPUs (30%% with 1-4 cpu/memory reservations), %d-pod FIFO queue (70%% cpuset LSR/LSE, 30%% "
+                   "GPU-share, 20%% reservation-owned, 80%% in 16 ElasticQuota groups), NodeResourcesFit+"
+                   "LoadAwareScheduling+NodeNUMAResource+DeviceShare+Reservation (w 1/1/1/1/5000)+ElasticQuota, "
+                   "batched exact rounds of 32 pods, %d pods per step",
+        "c3": "C3 cluster: %d nodes, %d-pod FIFO queue, NodeResourcesFit+LoadAwareScheduling, %d pods per step",
+        "c4": "C4 cluster: %d 2-socket 256-cpu nodes (node count: builder's choice, BASELINE names none), "
+              "%d-pod FIFO queue (70%% cpuset LSR/LSE), NodeResourcesFit+LoadAwareScheduling+NodeNUMAResource, "
+              "%d pods per step",
+        "c5ds": "C5 (DeviceShare part): %d nodes x 8 GPUs, %d-pod FIFO queue (30%% GPU-share), "
+                "NodeResourcesFit+LoadAwareScheduling+DeviceShare, %d pods per step",
+        "c5": "C5 (one profile): %d nodes x 8 GPUs (30%% with 1-4 cpu/memory reservations, 64 owner groups), "
+              "%d-pod FIFO queue (30%% GPU-share, 20%% reservation-owned, 80%% in 16 ElasticQuota groups), "
+              "NodeResourcesFit+LoadAwareScheduling+Reservation (w 5000)+DeviceShare+ElasticQuota admission, "
+              "batched exact rounds of 32 pods, %d pods per step",
+        "c5r": "C5 (Reservation part): %d nodes (30%% with 1-4 reservations), %d-pod FIFO queue (20%% "
+               "reservation-owned), NodeResourcesFit+LoadAwareScheduling+Reservation (w 5000), batched exact "
+               "rounds of 32 pods, %d pods per step",
+        "stock": "k8s v1.24 default profile + LoadAware: %d nodes (labels, NoSchedule / PreferNoSchedule taints), "
+                 "%d-pod FIFO queue of 8 deployments in 4 teams (40%% DoNotSchedule / 50%% ScheduleAnyway hostname "
+                 "spread, 15%% required anti-affinity, 10%% required affinity, 30%% preferred terms), NodeResourcesFit"
+                 "+LoadAware+TaintToleration+NodeAffinity+BalancedAllocation+PodTopologySpread(w2)+InterPodAffinity, "
+                 "one pod per exact pass, %d pods per step",
+        "stockz": "k8s v1.24 default profile + LoadAware with zone keys: %d nodes in 4 zones (5%% without the zone "
+                  "label), %d-pod FIFO queue of 8 deployments in 4 teams (hostname and zone spread constraints in "
+                  "random order; a third of required anti-affinity, half of required affinity and half of "
+                  "preferred terms zone-keyed), the stock profile's plugins and weights, one pod per exact pass, "
+                  "%d pods per step",
+    }[wl] % (n, total, args.pods_per_step)
+    return {
+        "metric": {"c3": "pods scheduled/sec at 100k nodes (node-evals/sec alongside)",
+                   "c1": "pods scheduled/sec, config 1 (500 nodes; node-evals/sec alongside)",
+                   "c2": "pods scheduled/sec, config 2 (10k nodes; node-evals/sec alongside)",
+                   "shipped": "pods scheduled/sec, the shipped koord-scheduler profile (node-evals/sec alongside)",
+                   "c4": "pods scheduled/sec, NodeNUMAResource cpuset/NUMA profile (node-evals/sec alongside)",
+                   "c5ds": "pods scheduled/sec, DeviceShare GPU-share profile (node-evals/sec alongside)",
+                   "c5r": "pods scheduled/sec, Reservation profile (node-evals/sec alongside)",
+                   "c5": "pods scheduled/sec, Reservation+DeviceShare+ElasticQuota profile (node-evals/sec "
+                         "alongside)",
+                   "stock": "pods scheduled/sec, default plugins + hostname PodTopologySpread / InterPodAffinity "
+                            "(node-evals/sec alongside)",
+                   "stockz": "pods scheduled/sec, default plugins + hostname / zone PodTopologySpread / "
+                             "InterPodAffinity (node-evals/sec alongside)"}[wl],
+        "value": pods_s,
+        "unit": "pods/s",
+        "n_gpus": d.world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak" if independent else "strong",
+        "vs_baseline": None,
+        "dtype": "int64",
+        "data": "synthetic (SURVEY §8d generator, seed %d)" % work.seed,
+        "config": {"workload": desc, "nodes": n, "pods": total, "batch_pods": args.batch,
+                   "pods_per_wave": args.pods_per_wave, "pipeline_depth": args.depth or "default",
+                   "parallelism": parallelism},
+        "node_evals_per_sec": pods_s * n,
+        "placed": placed,
+        "device_rounds": rounds,
+    }
 
 
 if __name__ == "__main__":

@@ -14,4 +14,4 @@ run() {  # name timeout cmd...
 }
 run smoke 240 python -u -c "import __graft_entry__ as g; g.smoke()"
 run tests 900 python -u -m pytest tests -x -v -m "gpu and not slow" --timeout 120 --timeout-method thread
-run bench_small 300 python -u bench.py --nodes 10000 --pods-per-step 10000 --steps 3 --no-cpu-baseline --kernel-iters 20
+run bench_small 300 python -u bench.py --full --nodes 10000 --pods-per-step 10000 --steps 3 --no-cpu-baseline --kernel-iters 20

@@ -12,11 +12,11 @@ mkdir -p $OUT
 BENCH=${BENCH_ARGS:-""}
 SHORT=${SHORT_ARGS:-"--steps 1 --pods-per-step 2000 --warmup 0 --no-cpu-baseline --kernel-iters 5"}
 echo "== kernel trace: bench.py $BENCH"
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 -u bench.py $BENCH > $OUT/trace.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 -u bench.py --full $BENCH > $OUT/trace.log 2>&1
 rc=$?; echo "trace rc=$rc"; tail -2 $OUT/trace.log; [ $rc -eq 0 ] || exit $rc
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "== pmc $c: bench.py $SHORT"
-  timeout -s KILL 120 rocprofv3 --pmc $c -d $OUT/pmc_$c -o run --output-format csv -- python3 -u bench.py $SHORT > $OUT/pmc_$c.log 2>&1
+  timeout -s KILL 120 rocprofv3 --pmc $c -d $OUT/pmc_$c -o run --output-format csv -- python3 -u bench.py --full $SHORT > $OUT/pmc_$c.log 2>&1
   rc=$?; echo "pmc $c rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done
 python3 scripts/pmc_summary.py $OUT > $OUT/summary.txt && cat $OUT/summary.txt

@@ -16,8 +16,8 @@ run() {  # name timeout cmd...
   [ $rc -eq 0 ] || exit $rc
 }
 [ -n "$SKIP_TESTS" ] || run tests 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread
-run bench_c3 600 python3 -u bench.py --cpu-nproc
-run bench_c1 300 python3 -u bench.py --workload c1
-run bench_c4 600 python3 -u bench.py --workload c4
-run bench_c5 600 python3 -u bench.py --workload c5
+run bench_c3 600 python3 -u bench.py --full --cpu-nproc
+run bench_c1 300 python3 -u bench.py --full --workload c1
+run bench_c4 600 python3 -u bench.py --full --workload c4
+run bench_c5 600 python3 -u bench.py --full --workload c5
 [ -n "$SKIP_PROF" ] || bash scripts/gpu_prof.sh

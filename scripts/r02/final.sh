@@ -15,9 +15,9 @@ run() {  # name timeout cmd...
 }
 run smoke 300 python3 -u -c "import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")"
 run tests 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread
-run bench_c4 600 python3 -u bench.py --workload c4
-run bench_c3 600 python3 -u bench.py
-run bench_c5 600 python3 -u bench.py --workload c5
-run prof_c4 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o c4 -- python3 -u bench.py \
+run bench_c4 600 python3 -u bench.py --full --workload c4
+run bench_c3 600 python3 -u bench.py --full
+run bench_c5 600 python3 -u bench.py --full --workload c5
+run prof_c4 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o c4 -- python3 -u bench.py --full \
   --workload c4 --steps 3 --no-cpu-baseline
 find $OUT/prof -name '*stats.csv'

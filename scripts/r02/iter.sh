@@ -13,5 +13,5 @@ for cfg in "100000 20000 1 32" "100000 20000 2 32" "100000 20000 3 32" "100000 2
   timeout -k 10 120 python3 -u scripts/stamps.py $cfg > $OUT/s_${cfg// /_}.log 2>&1
   rc=$?; head -2 $OUT/s_${cfg// /_}.log; [ $rc -eq 0 ] || exit $rc
 done
-timeout -k 10 400 python3 -u bench.py --steps 5 --warmup 1 --no-cpu-baseline ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 -u bench.py --full --steps 5 --warmup 1 --no-cpu-baseline ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench rc=$rc"; tail -n 2 $OUT/bench.err; cat $OUT/bench.json; exit $rc

@@ -16,10 +16,10 @@ for wl in ${WLS:-c3 c4 c5 c5ds}; do
   esac
   SHORT="--workload $wl $SHORT --warmup 0 --no-cpu-baseline --check 0 --profile-pods 0 --kernel-iters 2"
   echo "== $wl trace"
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 -u bench.py $SHORT > $OUT/trace.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 -u bench.py --full $SHORT > $OUT/trace.log 2>&1
   rc=$?; echo "trace rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/trace.log; exit $rc; }
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout -s KILL 200 rocprofv3 --pmc $c -d $OUT/pmc_$c -o run --output-format csv -- python3 -u bench.py $SHORT > $OUT/pmc_$c.log 2>&1
+    timeout -s KILL 200 rocprofv3 --pmc $c -d $OUT/pmc_$c -o run --output-format csv -- python3 -u bench.py --full $SHORT > $OUT/pmc_$c.log 2>&1
     rc=$?; echo "pmc $c rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/pmc_$c.log; exit $rc; }
   done
   META=$(python3 -c "import bench,json; n,_,b,p,_=bench.WORKLOADS['$wl']; print(json.dumps({'nodes':n,'batch_pods':b,'pods_per_wave':p,'depth':0,'workload':'$wl','command':'bench.py $SHORT'}))")

@@ -9,8 +9,8 @@ mkdir -p $OUT
 timeout -k 10 600 python -u -m pytest tests/test_reservation_gpu.py tests/test_c5_combined.py tests/test_unreserve.py \
   tests/test_elasticquota.py -x -q --timeout 300 --timeout-method thread > $OUT/tests.log 2>&1
 rc=$?; echo "tests rc=$rc"; tail -n 3 $OUT/tests.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python3 -u bench.py --workload c5 --steps 3 --no-cpu-baseline > $OUT/c5.json 2> $OUT/c5.err
+timeout -k 10 400 python3 -u bench.py --full --workload c5 --steps 3 --no-cpu-baseline > $OUT/c5.json 2> $OUT/c5.err
 rc=$?; echo "c5 rc=$rc"; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python3 -u bench.py --workload c5 --steps 40 --pods-per-step 8 --profile-pods 0 --no-cpu-baseline \
+timeout -k 10 400 python3 -u bench.py --full --workload c5 --steps 40 --pods-per-step 8 --profile-pods 0 --no-cpu-baseline \
   > $OUT/c5_small.json 2> $OUT/c5_small.err
 rc=$?; echo "c5 small rc=$rc"; exit $rc

@@ -15,7 +15,7 @@ run() {  # name timeout cmd...
   [ $rc -eq 0 ] || exit $rc
 }
 [ -n "$SKIP_TESTS" ] || run tests 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread
-run bench_c3 600 python3 -u bench.py ${C3_ARGS}
+run bench_c3 600 python3 -u bench.py --full ${C3_ARGS}
 [ -n "$ONLY_C3" ] && exit 0
-run bench_c5 600 python3 -u bench.py --workload c5
-run bench_c4 600 python3 -u bench.py --workload c4
+run bench_c5 600 python3 -u bench.py --full --workload c5
+run bench_c4 600 python3 -u bench.py --full --workload c4

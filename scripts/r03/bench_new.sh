@@ -14,7 +14,7 @@ run() {  # name timeout cmd...
   [ $rc -eq 0 ] || exit $rc
 }
 run tests 600 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu tests/test_shipped_profile.py
-run shipped 600 python3 -u bench.py --workload shipped --steps 3 --cpu-seconds 6
-run c2 400 python3 -u bench.py --workload c2 --cpu-seconds 6
-run c1 300 python3 -u bench.py --workload c1 --cpu-seconds 4
-run c3 600 python3 -u bench.py --steps 3 --no-cpu-baseline --check 2000
+run shipped 600 python3 -u bench.py --full --workload shipped --steps 3 --cpu-seconds 6
+run c2 400 python3 -u bench.py --full --workload c2 --cpu-seconds 6
+run c1 300 python3 -u bench.py --full --workload c1 --cpu-seconds 4
+run c3 600 python3 -u bench.py --full --steps 3 --no-cpu-baseline --check 2000

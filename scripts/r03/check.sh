@@ -14,4 +14,4 @@ run() {  # name timeout cmd...
   [ $rc -eq 0 ] || exit $rc
 }
 run tests 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread ${TESTS:-}
-[ -n "$NOBENCH" ] || run bench_c3 600 python3 -u bench.py --steps 5
+[ -n "$NOBENCH" ] || run bench_c3 600 python3 -u bench.py --full --steps 5

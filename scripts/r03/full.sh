@@ -15,5 +15,5 @@ run() {  # name timeout cmd...
 }
 run tests 1100 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread
 for w in ${BENCHES:-c3 c1}; do
-  run bench_$w 600 python3 -u bench.py --workload $w ${BENCH_ARGS:-}
+  run bench_$w 600 python3 -u bench.py --full --workload $w ${BENCH_ARGS:-}
 done

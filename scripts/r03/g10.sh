@@ -16,6 +16,6 @@ run() {  # name timeout cmd...
 }
 [ -n "$NOTESTS" ] || run tests 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread ${TESTS:-}
 for w in ${BENCHES:-c3}; do
-  run bench_$w 400 python3 -u bench.py --workload $w ${BARGS:-}
+  run bench_$w 400 python3 -u bench.py --full --workload $w ${BARGS:-}
 done
 [ -n "$NOROOF" ] || WL=c3 bash scripts/r03/roofline.sh

@@ -16,5 +16,5 @@ run() {  # name timeout cmd...
 run tests 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread
 TAILN=8 STAMPS_LIB=libkoordgpu_stamps.so run stamps_c4 300 python3 -u scripts/stamps_numa.py 10000 4000 16
 for w in ${BENCHES:-c4 c5 shipped}; do
-  run bench_$w 400 python3 -u bench.py --workload $w --steps 5 --cpu-seconds 4 --single-pod-calls 20
+  run bench_$w 400 python3 -u bench.py --full --workload $w --steps 5 --cpu-seconds 4 --single-pod-calls 20
 done

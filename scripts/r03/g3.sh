@@ -14,4 +14,4 @@ run() {  # name timeout cmd...
   [ $rc -eq 0 ] || exit $rc
 }
 run tests 600 python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu ${TESTS:-tests/test_dist_engine_gloo.py tests/test_multirank_loopback.py tests/test_parity_gpu.py}
-run bench_c3 600 python3 -u bench.py --steps 5 --no-cpu-baseline --check 10000 --single-pod-calls 50
+run bench_c3 600 python3 -u bench.py --full --steps 5 --no-cpu-baseline --check 10000 --single-pod-calls 50

@@ -17,5 +17,5 @@ run tests 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-met
 [ -n "$NOSTAMPS" ] || run stamps_c5 300 python3 -u scripts/stamps_xr.py c5 50000 3000
 [ -n "$NOSTAMPS" ] || run stamps_shipped 300 python3 -u scripts/stamps_xr.py shipped 50000 2000
 for w in ${BENCHES:-c5 shipped c4}; do
-  run bench_$w 400 python3 -u bench.py --workload $w --steps 5 --cpu-seconds 4 --single-pod-calls 20
+  run bench_$w 400 python3 -u bench.py --full --workload $w --steps 5 --cpu-seconds 4 --single-pod-calls 20
 done

@@ -18,6 +18,6 @@ run() {  # name timeout cmd...
 STAMPS_LIB=libkoordgpu_stamps.so run stamps_c4 300 python3 -u scripts/stamps_numa.py 10000 4000 16
 run stamps_shipped 300 python3 -u scripts/stamps_xr.py shipped 50000 2000
 for w in ${BENCHES:-c4 shipped}; do
-  run bench_$w 400 python3 -u bench.py --workload $w --steps 5 --cpu-seconds 4 --single-pod-calls 20
+  run bench_$w 400 python3 -u bench.py --full --workload $w --steps 5 --cpu-seconds 4 --single-pod-calls 20
 done
 [ -n "$NOROOF" ] || WL=c3 bash scripts/r03/roofline.sh

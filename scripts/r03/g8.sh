@@ -17,8 +17,8 @@ run() {  # name timeout cmd...
 [ -n "$NOTESTS" ] || run tests 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread ${TESTS:-}
 run stamps_c3 300 python3 -u scripts/stamps.py 100000 20000 2 32
 for w in ${BENCHES:-c3}; do
-  run bench_$w 400 python3 -u bench.py --workload $w --steps ${STEPS:-10} --cpu-seconds 4 --single-pod-calls 20
+  run bench_$w 400 python3 -u bench.py --full --workload $w --steps ${STEPS:-10} --cpu-seconds 4 --single-pod-calls 20
 done
 SHORT="--workload c3 --steps 1 --pods-per-step 8000 --warmup 0 --no-cpu-baseline --check 0 --profile-pods 0 --kernel-iters 2 --single-pod-calls 0 --no-pcie"
-run trace_c3 300 rocprofv3 --kernel-trace --stats -d $out/trace -o run --output-format csv -- python3 -u bench.py $SHORT
+run trace_c3 300 rocprofv3 --kernel-trace --stats -d $out/trace -o run --output-format csv -- python3 -u bench.py --full $SHORT
 python3 scripts/trace_summary.py $out/trace 2>/dev/null | head -12 || true

@@ -15,5 +15,5 @@ run() {  # name timeout cmd...
 }
 TAILN=20 STAMPS_LIB=libkoordgpu_stamps.so run stamps_c4 300 python3 -u scripts/stamps_numa.py 10000 4000 16
 for w in ${BENCHES:-c3}; do
-  run bench_$w 400 python3 -u bench.py --workload $w --steps ${STEPS:-10} --cpu-seconds 4 --single-pod-calls 20
+  run bench_$w 400 python3 -u bench.py --full --workload $w --steps ${STEPS:-10} --cpu-seconds 4 --single-pod-calls 20
 done

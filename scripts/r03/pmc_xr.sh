@@ -15,7 +15,7 @@ groups=("SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_
 [ -n "$GROUPS_N" ] && groups=("${groups[@]:0:$GROUPS_N}")
 for grp in "${groups[@]}"; do
   i=$((i+1))
-  timeout -s KILL 150 rocprofv3 --pmc $grp -d $OUT/p$i -o run --output-format csv -- python3 -u bench.py $args > $OUT/p$i.log 2>&1
+  timeout -s KILL 150 rocprofv3 --pmc $grp -d $OUT/p$i -o run --output-format csv -- python3 -u bench.py --full $args > $OUT/p$i.log 2>&1
   rc=$?; echo "pass $i rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/p$i.log; exit $rc; }
 done
 python3 scripts/pmc_kernels.py $OUT

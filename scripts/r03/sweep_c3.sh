@@ -10,7 +10,7 @@ for cfg in ${CFGS:-"8 32 2" "4 32 2" "2 32 2" "4 32 3" "4 48 2" "8 64 2" "4 64 2
   set -- $cfg
   name="ppw$1_b$2_d$3"
   echo "== $name"
-  timeout -k 10 300 python3 -u bench.py --steps 3 --no-cpu-baseline --check 0 --single-pod-calls 0 \
+  timeout -k 10 300 python3 -u bench.py --full --steps 3 --no-cpu-baseline --check 0 --single-pod-calls 0 \
     --pods-per-wave $1 --batch $2 --depth $3 ${BENCH_ARGS:-} > "$out/$name.json" 2> "$out/$name.err"
   rc=$?
   echo "$name rc=$rc"

@@ -15,5 +15,5 @@ run() {  # name timeout cmd...
 }
 run tests 600 python -u -m pytest -x -q -m gpu --timeout 200 --timeout-method thread ${TESTS:-tests/test_c5_combined.py tests/test_reservation_gpu.py tests/test_shipped_profile.py tests/test_default_plugins.py tests/test_single_pod.py tests/test_reservation_restore.py tests/test_golden_reservation.py tests/test_unreserve.py}
 for w in ${BENCHES:-shipped c5}; do
-  run bench_$w 400 python3 -u bench.py --workload $w ${BENCH_ARGS:-}
+  run bench_$w 400 python3 -u bench.py --full --workload $w ${BENCH_ARGS:-}
 done

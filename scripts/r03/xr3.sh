@@ -18,7 +18,7 @@ run stamps_c5 300 python3 -u scripts/stamps_xr.py c5 50000 3000
 run stamps_shipped 300 python3 -u scripts/stamps_xr.py shipped 50000 2000
 run stamps_c3 300 python3 -u scripts/stamps.py 100000 20000 2 32
 for w in ${BENCHES:-c5 shipped c5r}; do
-  run bench_$w 400 python3 -u bench.py --workload $w --steps 5 --cpu-seconds 4 --single-pod-calls 50
+  run bench_$w 400 python3 -u bench.py --full --workload $w --steps 5 --cpu-seconds 4 --single-pod-calls 50
 done
 [ -n "$NOPMC" ] || TAG=${TAG:-xr3}/pmc_c5 WL=c5 GROUPS_N=2 timeout -k 10 600 bash scripts/r03/pmc_xr.sh > $out/pmc.log 2>&1
 echo "pmc rc=$?"; tail -n 14 $out/pmc.log | cut -c1-700

@@ -12,7 +12,7 @@ fi
 for lib in ${LIBS:-}; do
   tag=$(basename $lib .so)
   for wl in ${WLS:-stock}; do
-    KOORDGPU_LIB=$PWD/$lib timeout -k 10 ${T:-240} python3 -u bench.py --workload $wl --no-cpu-baseline --no-pcie \
+    KOORDGPU_LIB=$PWD/$lib timeout -k 10 ${T:-240} python3 -u bench.py --full --workload $wl --no-cpu-baseline --no-pcie \
       --single-pod-calls 0 ${EXTRA:-} > gpurun_out/r06/ab/${wl}_$tag.json 2> gpurun_out/r06/ab/${wl}_$tag.err
     rc=$?; [ $rc -eq 0 ] || { echo "$wl $tag rc=$rc"; tail -5 gpurun_out/r06/ab/${wl}_$tag.err; exit $rc; }
     python3 - gpurun_out/r06/ab/${wl}_$tag.json "$wl $tag" <<'PY'

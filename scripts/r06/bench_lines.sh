@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out/r06
 for spec in ${SPECS:-"c3:20:5" "c4:5:1" "shipped:5:1"}; do
   IFS=: read wl steps warm <<< "$spec"
-  timeout -k 10 ${T:-420} python3 -u bench.py --workload $wl --steps $steps --warmup $warm ${EXTRA:-} \
+  timeout -k 10 ${T:-420} python3 -u bench.py --full --workload $wl --steps $steps --warmup $warm ${EXTRA:-} \
     > gpurun_out/r06/bench_$wl.json 2> gpurun_out/r06/bench_$wl.err
   rc=$?; echo "$wl rc=$rc"; [ $rc -eq 0 ] || { tail -5 gpurun_out/r06/bench_$wl.err; exit $rc; }
   python3 - "$wl" <<'PY'

@@ -8,7 +8,7 @@ OUT=gpurun_out/r06/${NAME:-c3_sweep}.txt
 : > $OUT
 for cfg in ${CFGS:-"2:38" "3:38" "3:32" "3:44" "4:32" "2:40"}; do
   d=${cfg%%:*}; b=${cfg##*:}
-  timeout -k 10 240 python3 -u bench.py --steps ${STEPS:-3} --warmup 1 --depth $d --batch $b --no-cpu-baseline --no-pcie \
+  timeout -k 10 240 python3 -u bench.py --full --steps ${STEPS:-3} --warmup 1 --depth $d --batch $b --no-cpu-baseline --no-pcie \
     --single-pod-calls 0 --check 0 --profile-pods 5000 ${EXTRA:-} > gpurun_out/r06/sweep_one.json 2> gpurun_out/r06/sweep_one.err
   rc=$?
   [ $rc -eq 0 ] || { echo "depth $d batch $b rc=$rc"; tail -5 gpurun_out/r06/sweep_one.err; exit $rc; }
