@@ -34,6 +34,8 @@
  *   kg_quotas_set           ElasticQuota PreFilter/Reserve state: per quota used / non-preemptible used (QuotaInfo,
  *                           elasticquota/core/quota_info.go) and usedLimit (getQuotaInfoUsedLimit: runtime or max,
  *                           elasticquota/plugin_helper.go:237-246) + min, as the Go GroupQuotaManager holds them.
+ *   kg_debug_topn           frameworkext's --debug-scores table (frameworkext/debug.go:61-108): the N best nodes of one
+ *                           pod with their total and one column per Score plugin, ranked on the device.
  *   kg_last_error           error text for the last failing call on this thread (maps to framework.NewStatus(Error,…)).
  *
  * Units follow the reference's getResourceValue (load_aware/helper.go:146-151): cpu-like resources in
@@ -48,7 +50,7 @@
 extern "C" {
 #endif
 
-#define KG_ABI_VERSION 17
+#define KG_ABI_VERSION 18
 
 /* ---- resource slots (fixed order) ------------------------------------------------------- */
 enum {
@@ -820,10 +822,39 @@ int kg_debug_stamps(kg_engine* e, uint64_t* out);
  * multi-GPU run takes. */
 int kg_debug_rccl_selftest(int device_id, int64_t n);
 
+/* (ABI 18) The --debug-scores table of one pod (frameworkext/debug.go:61-108 debugScores), ranked on the device: the
+ * `topn` best feasible nodes with their total score and one column per Score plugin.
+ *   - No state change.  The pod is evaluated on every valid node exactly as kg_pods_schedule would evaluate it as the
+ *     next pod — the clock and expired-metric handling, the BeforePreFilter restore, every enabled Filter, the
+ *     nomination, the preferred-node score of 1000 — but nothing is assumed: the device state, the staged queue, the
+ *     results buffers and the scheduling pass's scratch are the same after the call as before it.
+ *   - Rows.  The feasible nodes ordered by total descending, ties on the lowest node index (the reference's sort.Slice
+ *     is unstable; this is the rule BASELINE pins for selectHost).  *out_n_rows = min(topn, feasible); *out_feasible is
+ *     the feasibleNodes of debug.go:107.  Rows past *out_n_rows are left untouched.
+ *   - Invariants.  plugin[] over the enabled columns sums to total.  Row 0 is the node and score kg_pods_schedule
+ *     returns for that pod.
+ *   - ElasticQuota admission is not consulted: it is a PreFilter, and the reference prints the table only after scoring.
+ *   - Errors.  topn outside 1..KG_TOPN_MAX or a null argument: KG_E_INVALID.  KG_E_UNSUPPORTED, with a message saying
+ *     which: a PodTopologySpread / InterPodAffinity profile (their cluster-wide reductions, as for
+ *     kg_pods_evaluate_reservation), or an engine that shards nodes over ranks (kg_engine_ranks shard_ranks > 1).
+ * One device-to-host copy of topn rows and the two counters; no n-sized copy, no ranking on the host. */
+#define KG_TOPN_MAX 64
+enum { KG_PL_FIT = 0, KG_PL_LOADAWARE, KG_PL_NUMA, KG_PL_DEVICESHARE, KG_PL_RESERVATION, KG_PL_TAINT,
+       KG_PL_NODE_AFFINITY, KG_PL_BALANCED, KG_PL_IMAGE_LOCALITY, KG_PL_COLUMNS = 16 };
+typedef struct {
+  int32_t node_idx;   /* node slot */
+  int32_t nominated;  /* reservation slot nominated on that node, -1 = none / no Reservation */
+  int64_t total;      /* what kg_pods_schedule would report as the node's score */
+  int64_t plugin[KG_PL_COLUMNS]; /* weighted, normalised Score per plugin as RunScorePlugins returns it;
+                                    -1 = plugin not enabled at Score in this profile (debug.go:100-101) */
+} kg_topn_row;
+int kg_debug_topn(kg_engine* e, const kg_pod* pod, int32_t topn, kg_topn_row* out_rows, int64_t* out_n_rows,
+                  int64_t* out_feasible);
+
 const char* kg_last_error(void);
 int kg_abi_version(void);
 /* sizeof of the ABI structs (0 kg_config, 1 kg_node, 2 kg_node_metric, 3 kg_pod, 4 kg_stats, 5 kg_node_numa,
- * 6 kg_node_device, 7 kg_quota, 8 kg_node_reservations, 9 kg_pod_metric, 10 kg_node_predicates) for
+ * 6 kg_node_device, 7 kg_quota, 8 kg_node_reservations, 9 kg_pod_metric, 10 kg_node_predicates, 11 kg_topn_row) for
  * binding checks. */
 int64_t kg_abi_struct_size(int which);
 

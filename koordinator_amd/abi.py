@@ -36,7 +36,7 @@ POD_TAINT_TABLE = 64
 MAX_OWNER_GROUPS = 64
 QUOTA_RES = 8
 MAX_QUOTAS = 64
-ABI_VERSION = 17
+ABI_VERSION = 18
 MAX_RSV_SLOTS = 4
 RSV_POLICY = {"Default": 0, "Aligned": 1, "Restricted": 2}
 POD_RSV_AFFINITY, POD_RSV_OPERATING = 1, 2
@@ -207,8 +207,17 @@ STATS_DTYPE = np.dtype([
     ("seconds", np.float64), ("reserved", np.float64, (3,)),
 ])
 
+# (ABI 18) kg_debug_topn: one row of the --debug-scores table; plugin[KG_PL_*] = the weighted, normalised Score of that
+# plugin, -1 = not enabled at Score in the profile
+TOPN_MAX = 64  # KG_TOPN_MAX
+PL_FIT, PL_LOADAWARE, PL_NUMA, PL_DEVICESHARE, PL_RESERVATION, PL_TAINT, PL_NODE_AFFINITY, PL_BALANCED, \
+    PL_IMAGE_LOCALITY = range(9)
+PL_COLUMNS = 16  # KG_PL_COLUMNS
+TOPN_ROW_DTYPE = np.dtype([("node_idx", np.int32), ("nominated", np.int32), _i64("total"), _i64("plugin", PL_COLUMNS)])
+
 STRUCT_DTYPES = {0: CONFIG_DTYPE, 1: NODE_DTYPE, 2: METRIC_DTYPE, 3: POD_DTYPE, 4: STATS_DTYPE, 5: NODE_NUMA_DTYPE,
-                 6: NODE_DEVICE_DTYPE, 7: QUOTA_DTYPE, 8: NODE_RSV_DTYPE, 9: POD_METRIC_DTYPE, 10: NODE_PRED_DTYPE}
+                 6: NODE_DEVICE_DTYPE, 7: QUOTA_DTYPE, 8: NODE_RSV_DTYPE, 9: POD_METRIC_DTYPE, 10: NODE_PRED_DTYPE,
+                 11: TOPN_ROW_DTYPE}
 
 # Every symbol include/koordgpu.h declares (tests check the library exports all of them).
 EXPORTED_SYMBOLS = (
@@ -227,7 +236,7 @@ EXPORTED_SYMBOLS = (
     "kg_loopback_destroy", "kg_engine_create_loopback", "kg_pods_unreserve", "kg_engine_set_clock",
     "kg_node_pods_metric_set", "kg_debug_numa_merge", "kg_pods_evaluate_reservation", "kg_nodes_predicates_upsert",
     "kg_engine_create_hosted", "kg_pods_filter_preemption", "kg_nodes_read_pod_groups",
-    "kg_pods_select_victims",
+    "kg_pods_select_victims", "kg_debug_topn",
 )
 
 # int (*kg_exchange_fn)(void* user, const void* send, void* recv, int64_t bytes)
@@ -322,6 +331,7 @@ def load_library(path: str | None = None):
         "kg_pods_select_victims": (i, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kg_nodes_read_pod_groups": (i, [vp, vp, vp, vp, vp, vp]),
         "kg_nodes_predicates_upsert": (i, [vp, vp, vp, i64]),
+        "kg_debug_topn": (i, [vp, vp, ctypes.c_int32, vp, vp, vp]),
         "kg_engine_create_hosted": (i, [vp, i64, i, i, EXCHANGE_FN, vp, ctypes.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():

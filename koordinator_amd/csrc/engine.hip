@@ -3496,6 +3496,7 @@ __global__ void select_victims(DevTable T, const RsvNode* __restrict__ RN, const
 
 // Scatter of upserted device rows
 #include "xr_dev.h"
+#include "topn_dev.h"
 
 template <typename Rec>
 __global__ void scatter_rows(Rec* __restrict__ dst, const Rec* __restrict__ src, const int32_t* __restrict__ idx,
@@ -3897,6 +3898,7 @@ struct kg_engine {
   hipEvent_t ev_res[kMaxDepth] = {};
   DevBuf<RowDelta> deltas;
   DevBuf<int64_t> scratch64;
+  DevBuf<uint64_t> topn_buf;   // kg_debug_topn's own scratch: values, partials, candidates, the pod, the rows
   DevBuf<int32_t> scratch32;
   std::vector<int64_t> h_static64;
   std::vector<int32_t> h_static32;
@@ -5719,6 +5721,7 @@ int64_t kg_abi_struct_size(int which) {
     case 8: return sizeof(kg_node_reservations);
     case 9: return sizeof(kg_pod_metric);
     case 10: return sizeof(kg_node_predicates);
+    case 11: return sizeof(kg_topn_row);
   }
   return -1;
 }
@@ -6237,6 +6240,7 @@ void kg_engine_destroy(kg_engine* e) {
   e->gz.release();
   e->gzm.release();
   e->scratch64.release();
+  e->topn_buf.release();
   e->scratch32.release();
   e->uidx.release();
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -7549,6 +7553,120 @@ int kg_pods_evaluate_reservation(kg_engine* e, const kg_pod* pod, int64_t* out) 
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, e->scratch64.p, words * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+// (ABI 18) the --debug-scores table of one pod, ranked on the device (topn_dev.h): evaluate → select → final → gather,
+// plain launches in stream order over e->topn_buf, then one copy of the header and `topn` rows.  The per-node body is
+// rsv_eval_node — the exact pass's, which also serves single-pod schedule calls of every profile — so the table is what
+// kg_pods_schedule would compute for the pod as the next one; the scheduling buffers (rsv_val, rsv_part, rsv_ws, numa_aff,
+// the DeviceShare normalisation buffers, the staged queue and its results) are neither read nor written.
+int kg_debug_topn(kg_engine* e, const kg_pod* pod, int32_t topn, kg_topn_row* out_rows, int64_t* out_n_rows,
+                  int64_t* out_feasible) {
+  if (!e || !pod || !out_rows || !out_n_rows || !out_feasible) return fail(KG_E_INVALID, "null argument");
+  if (topn < 1 || topn > KG_TOPN_MAX) return fail(KG_E_INVALID, "topn %d outside 1..%d", (int)topn, KG_TOPN_MAX);
+  if (e->grp_on)
+    return fail(KG_E_UNSUPPORTED, "kg_debug_topn: PodTopologySpread / InterPodAffinity need the pass's cluster-wide "
+                "reductions (the Go path prints their table)");
+  if (e->n_ranks > 1)
+    return fail(KG_E_UNSUPPORTED, "kg_debug_topn: the engine shards nodes over %d ranks (a rank holds a part of the "
+                "table; use a one-rank or replica engine)", e->n_ranks);
+  if (int rc = sync_static(e)) return rc;
+  DevPod d;
+  if (int rc = decode_pod(e, *pod, d)) return rc;
+  int64_t rq[kAux];
+  for (int q = 0; q < kAux; ++q) rq[q] = pod->requests[kAuxFirst + q];
+  RsvPod rp;
+  RsvSel rs;
+  if (int rc = decode_rsv_pod(*pod, rp, rs, 0)) return rc;
+  if (int rc = check_rsv_predicates(e, rsv_pred_top(rp, rs))) return rc;
+  if (rp.flags & RP_SEL) rp.aux = 0;  // the scratch copy below
+  DsPod dsp{};
+  dsp.skip = 1;
+  if (e->ds_on) {
+    if (int rc = decode_ds_pod(*pod, dsp)) return rc;
+    if ((dsp.xq[0] | dsp.xq[1]) != 0 && e->rsv_on && e->rgpu_nodes > 0)
+      return fail(KG_E_UNSUPPORTED, "RDMA / FPGA requests with reservations that hold GPUs keep the Go path");
+  } else {
+    for (int r = 0; r < KG_DEV_RES_MAX; ++r)
+      if (pod->device_requests[r] != 0 && e->cfg.fit_filter)
+        return fail(KG_E_UNSUPPORTED, "the pod requests devices; the profile has no DeviceShare");
+  }
+  NumaPod np{};
+  if (e->numa_on)
+    if (int rc = decode_numa_pod(e->cfg, *pod, np)) return rc;
+  DefPod df{};
+  if (e->def_on) {
+    if (int rc = decode_def_pod(*pod, df, 0)) return rc;
+    if (int rc = check_pod_tables(e, *pod)) return rc;
+  }
+  const int64_t n = e->n_nodes;
+  *out_n_rows = 0;
+  *out_feasible = 0;
+  if (n == 0) return 0;
+  const int64_t nb = (n + kRsvThreads - 1) / kRsvThreads;
+  constexpr int64_t kRowWords = (int64_t)(sizeof(kg_topn_row) / 8), kHdrWords = (int64_t)(sizeof(TopnHdr) / 8);
+  static_assert(sizeof(kg_topn_row) % 8 == 0 && sizeof(RsvPod) % 8 == 0 && sizeof(RsvSel) % 8 == 0, "topn scratch layout");
+  // word offsets into the scratch
+  const int64_t o_val = 0, o_val2 = o_val + n, o_part = o_val2 + (n + 1) / 2, o_cand = o_part + 6 * nb,
+                o_win = o_cand + nb * topn, o_pod = o_win + KG_TOPN_MAX, o_rpod = o_pod + kPodWords,
+                o_dpod = o_rpod + (int64_t)(sizeof(RsvPod) / 8), o_npod = o_dpod + kDsPodWords,
+                o_sel = o_npod + kNumaPodWords, o_aux = o_sel + (int64_t)(sizeof(RsvSel) / 8), o_df = o_aux + kAux,
+                o_out = o_df + (int64_t)((sizeof(DefPod) + 7) / 8), words = o_out + kHdrWords + kRowWords * KG_TOPN_MAX;
+  if (int rc = e->topn_buf.ensure((size_t)words)) return rc;
+  uint64_t* b = e->topn_buf.p;
+  DevPod* gp = reinterpret_cast<DevPod*>(b + o_pod);
+  RsvPod* gr = reinterpret_cast<RsvPod*>(b + o_rpod);
+  DsPod* gd = reinterpret_cast<DsPod*>(b + o_dpod);
+  NumaPod* gn = reinterpret_cast<NumaPod*>(b + o_npod);
+  RsvSel* gs = reinterpret_cast<RsvSel*>(b + o_sel);
+  int64_t* ga = reinterpret_cast<int64_t*>(b + o_aux);
+  DefPod* gf = reinterpret_cast<DefPod*>(b + o_df);
+  TopnHdr* gh = reinterpret_cast<TopnHdr*>(b + o_out);
+  kg_topn_row* grows = reinterpret_cast<kg_topn_row*>(b + o_out + kHdrWords);
+  // the pod's records are adjacent in the scratch: packed on the host, one copy (hp lives until the stream is synchronised)
+  uint64_t hp[(sizeof(DevPod) + sizeof(RsvPod) + sizeof(DsPod) + sizeof(NumaPod) + sizeof(RsvSel) + sizeof(rq) +
+               sizeof(DefPod) + 7 * 8) / 8] = {};
+  static_assert(sizeof(DevPod) == kPodWords * 8 && sizeof(DsPod) <= kDsPodWords * 8 && sizeof(NumaPod) <= kNumaPodWords * 8,
+                "topn pod records");
+  if ((size_t)(o_out - o_pod) * 8 > sizeof(hp)) return fail(KG_E_INVALID, "kg_debug_topn: pod record layout");
+  std::memcpy(hp + (o_pod - o_pod), &d, sizeof(d));
+  std::memcpy(hp + (o_rpod - o_pod), &rp, sizeof(rp));
+  std::memcpy(hp + (o_dpod - o_pod), &dsp, sizeof(dsp));
+  std::memcpy(hp + (o_npod - o_pod), &np, sizeof(np));
+  std::memcpy(hp + (o_sel - o_pod), &rs, sizeof(rs));
+  std::memcpy(hp + (o_aux - o_pod), rq, sizeof(rq));
+  std::memcpy(hp + (o_df - o_pod), &df, sizeof(df));
+  HIP_TRY(hipMemcpyAsync(gp, hp, (size_t)(o_out - o_pod) * 8, hipMemcpyHostToDevice, e->stream));
+  RsvExt X = rsv_ext(e);
+  X.rsv_sel = gs;
+  X.aff = nullptr;  // no pass affinity store: this is not a scheduling pass
+  X.val2 = e->def_score ? reinterpret_cast<uint32_t*>(b + o_val2) : nullptr;
+  X.gpods = nullptr;
+  const TopnPod tp{gp, gr, e->ds_on ? gd : nullptr, e->numa_on ? gn : nullptr, (d.flags & P_AUX) ? ga : nullptr,
+                   e->def_on ? gf : nullptr};
+  const kg_config& c = e->cfg;
+  const uint32_t en = (c.fit_score ? 1u << KG_PL_FIT : 0u) | (c.la_score ? 1u << KG_PL_LOADAWARE : 0u) |
+                      (c.numa_score ? 1u << KG_PL_NUMA : 0u) | (c.ds_score ? 1u << KG_PL_DEVICESHARE : 0u) |
+                      (c.reservation_score ? 1u << KG_PL_RESERVATION : 0u) | (c.taint_score ? 1u << KG_PL_TAINT : 0u) |
+                      (c.affinity_score ? 1u << KG_PL_NODE_AFFINITY : 0u) | (c.balanced_score ? 1u << KG_PL_BALANCED : 0u) |
+                      (c.image_score ? 1u << KG_PL_IMAGE_LOCALITY : 0u);
+  topn_eval<<<(unsigned)nb, kRsvThreads, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, tp, n, e->P, e->RP, X, b + o_val,
+                                                         b + o_part);
+  topn_select<<<(unsigned)nb, kRsvThreads, 0, e->stream>>>(b + o_val, n, (int)topn, e->RP, X, b + o_part, b + o_cand);
+  topn_final<<<1, kTopnFinalThreads, 0, e->stream>>>(b + o_cand, nb * topn, (int)nb, (int)topn, b + o_part, b + o_win, gh);
+  topn_gather<<<1, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, tp, (int)nb, e->P, e->RP, X, b + o_part,
+                                          b + o_win, gh, en, grows);
+  HIP_TRY(hipGetLastError());
+  std::vector<uint64_t> host((size_t)(kHdrWords + kRowWords * topn));
+  HIP_TRY(hipMemcpyAsync(host.data(), b + o_out, host.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  TopnHdr h;
+  std::memcpy(&h, host.data(), sizeof(h));
+  if (h.n_rows < 0 || h.n_rows > topn) return fail(KG_E_DEVICE, "kg_debug_topn: %lld rows", (long long)h.n_rows);
+  std::memcpy(out_rows, host.data() + kHdrWords, (size_t)h.n_rows * sizeof(kg_topn_row));
+  *out_n_rows = h.n_rows;
+  *out_feasible = h.feasible;
   return 0;
 }
 

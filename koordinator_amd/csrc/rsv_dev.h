@@ -212,6 +212,9 @@ struct RsvDbg {
   int32_t has_state;      // a nodeReservationState exists (BeforePreFilter restored the node)
   int64_t req_cpu, req_mem, nz_cpu, nz_mem, num_pods;  // the restored NodeInfo
   int64_t pod_req_cpu, pod_req_mem;                    // nodeReservationState.podRequested
+  // (ABI 18) the weighted parts of RsvOut::base, per plugin (kg_debug_topn's columns; 0 where the plugin does not score).
+  // w_numa includes the preferred-cpus delta of a pod nominated into a reservation holding cpus.
+  int64_t w_fit, w_la, w_numa, w_bal, w_img;
 };
 
 // BeforePreFilter's restore of one node for one pod (transformer.go:100-189): the matched slots' reserve pods leave
@@ -406,6 +409,7 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
     dbg->req_cpu = r.req_cpu, dbg->req_mem = r.req_mem, dbg->nz_cpu = r.nz_cpu, dbg->nz_mem = r.nz_mem;
     dbg->num_pods = r.num_pods;
     dbg->pod_req_cpu = has_state ? pr_c : 0, dbg->pod_req_mem = has_state ? pr_m : 0;
+    dbg->w_fit = dbg->w_la = dbg->w_numa = dbg->w_bal = dbg->w_img = 0;
   }
   if (dbg && df && !defaults_filter(npd, *df, X.DF)) return o;
   // Reservation.Filter of a reserve pod / a pod in reservation operating mode (plugin.go:324-350): the reservation's
@@ -421,7 +425,13 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
     }
   }
   int64_t t = 0;
-  if (!eval_node(r, p, P, t)) return o;  // NodeResourcesFit + LoadAware on the restored NodeInfo
+  if (dbg) {  // the same call with the two plugins' Scores reported
+    int64_t fs = 0, ls = 0;
+    const bool ok = eval_node(r, p, P, t, nullptr, &fs, &ls);
+    dbg->w_fit = P.fit_score ? fs * P.weight_fit : 0;
+    dbg->w_la = P.la_score ? ls * P.weight_la : 0;
+    if (!ok) return o;
+  } else if (!eval_node(r, p, P, t)) return o;  // NodeResourcesFit + LoadAware on the restored NodeInfo
   // fitsRequest over ephemeral-storage and the scalar resources the pod requests (reservation/plugin.go:469-479)
   if (aux_req && P.fit_filter && !aux_fits(T, i, aux_req)) return o;
   // satisfied(s): filterWithReservations([s]) (plugin.go:384-428) with fitsNode (:433-482), preemptible = 0
@@ -498,11 +508,16 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
     const NumaView nv = make_view(X.ns + i, X.nm + i, X.NP);
     if (!numa_eval(nv, *np, X.NP, r.req_cpu, r.req_mem, r.alloc_cpu, r.alloc_mem, nsc, naff)) return o;
     if (X.NP.score) t += nsc * X.NP.weight;
+    if (dbg && X.NP.score) dbg->w_numa = nsc * X.NP.weight;
     if (X.aff) X.aff[i] = naff.nil ? 0x100u : naff.mask;
   }
   if (df) {  // BalancedAllocation on the restored NodeInfo; the two normalised raw Scores
     if (X.DF.bal) t += X.DF.w_bal * balanced_score(r.alloc_cpu, r.alloc_mem, r.req_cpu, r.req_mem, p.req_cpu, p.req_mem, X.DF);
     if (X.DF.img) t += X.DF.w_img * image_score(npd, *df);
+    if (dbg) {  // the two terms just added, named
+      if (X.DF.bal) dbg->w_bal = X.DF.w_bal * balanced_score(r.alloc_cpu, r.alloc_mem, r.req_cpu, r.req_mem, p.req_cpu, p.req_mem, X.DF);
+      if (X.DF.img) dbg->w_img = X.DF.w_img * image_score(npd, *df);
+    }
     o.tcnt = X.DF.taint_score ? taint_raw(npd, *df) : 0;
     o.asum = X.DF.aff_score ? affinity_raw(npd, *df) : 0;
   }
@@ -569,6 +584,7 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
         const int64_t psc = numa_score_pref(X.ns[i], X.nm[i], nv, *np, X.NP, naff, P, r.req_cpu, r.req_mem,
                                             r.alloc_cpu, r.alloc_mem);
         o.base += (psc - nsc) * X.NP.weight;
+        if (dbg) dbg->w_numa += (psc - nsc) * X.NP.weight;
       }
     }
   }

@@ -432,6 +432,21 @@ class Engine:
                  "nonzero_mem", "num_pods", "pod_requested_cpu", "pod_requested_mem", "base", "ds_raw", "order")
         return {k: out[:, q] for q, k in enumerate(names)}
 
+    def debug_topn(self, pod: np.ndarray, topn: int, out: np.ndarray | None = None):
+        """(ABI 18) kg_debug_topn: the --debug-scores table of one pod, ranked on the device.  Returns (rows, feasible):
+        rows = the min(topn, feasible) best feasible nodes as abi.TOPN_ROW_DTYPE (total descending, ties on the lowest
+        node index; plugin[abi.PL_*] = each plugin's weighted, normalised Score, -1 = not enabled at Score), feasible =
+        the number of feasible nodes.  Nothing is assumed: the engine's state is unchanged.  `out`: a caller-owned
+        TOPN_ROW_DTYPE array of at least `topn` rows to fill (rows past the returned ones are left untouched)."""
+        pod = np.ascontiguousarray(np.asarray(pod, dtype=abi.POD_DTYPE).reshape(1))
+        if out is None:
+            out = np.zeros(max(int(topn), 1), dtype=abi.TOPN_ROW_DTYPE)
+        elif out.dtype != abi.TOPN_ROW_DTYPE or not out.flags["C_CONTIGUOUS"] or len(out) < int(topn):
+            raise ValueError("out: a C-contiguous TOPN_ROW_DTYPE array of at least topn rows")
+        counts = np.zeros(2, dtype=np.int64)
+        check(self.lib, self.lib.kg_debug_topn(self.h, ptr(pod), int(topn), ptr(out), ptr(counts[0:1]), ptr(counts[1:2])))
+        return out[:int(counts[0])], int(counts[1])
+
     def debug_numa_merge(self, cases: np.ndarray) -> np.ndarray:
         """The device topology-manager policy merge on int64[n, DBG_MERGE_WORDS] cases (kg_debug_numa_merge);
         returns int64[n, 8]: admit, nil, mask, preferred, score."""

@@ -36,6 +36,35 @@ IMAGE_LOCALITY = "ImageLocality"
 # (ABI 12) hostname-keyed PodTopologySpread (default weight 2) and InterPodAffinity (default weight 1)
 POD_TOPOLOGY_SPREAD, INTER_POD_AFFINITY = "PodTopologySpread", "InterPodAffinity"
 
+# (ABI 18) kg_topn_row.plugin[KG_PL_*] -> the plugin's name (the column headers of --debug-scores)
+PLUGIN_COLUMNS = {
+    abi.PL_FIT: NODE_RESOURCES_FIT, abi.PL_LOADAWARE: LOAD_AWARE, abi.PL_NUMA: NODE_NUMA_RESOURCE,
+    abi.PL_DEVICESHARE: DEVICE_SHARE, abi.PL_RESERVATION: RESERVATION, abi.PL_TAINT: TAINT_TOLERATION,
+    abi.PL_NODE_AFFINITY: NODE_AFFINITY, abi.PL_BALANCED: BALANCED_ALLOCATION, abi.PL_IMAGE_LOCALITY: IMAGE_LOCALITY,
+}
+# the kg_config field that enables each column's plugin at Score
+_PLUGIN_SCORE_FIELD = {
+    abi.PL_FIT: "fit_score", abi.PL_LOADAWARE: "la_score", abi.PL_NUMA: "numa_score", abi.PL_DEVICESHARE: "ds_score",
+    abi.PL_RESERVATION: "reservation_score", abi.PL_TAINT: "taint_score", abi.PL_NODE_AFFINITY: "affinity_score",
+    abi.PL_BALANCED: "balanced_score", abi.PL_IMAGE_LOCALITY: "image_score",
+}
+
+
+def render_debug_table(rows, plugin_columns, pod_ref: str, node_names) -> str:
+    """The Markdown table frameworkext's debugScores renders (frameworkext/debug.go:83-107, go-pretty RenderMarkdown):
+    header `#`, `Pod`, `Node`, `Score`, then the plugin names sorted as strings; one line per row, in the order given
+    (kg_debug_topn ranks them).  rows: kg_topn_row records or plain mappings with "node_idx", "total" and "plugin"
+    (indexable by column); plugin_columns: {column: plugin name} of the columns to print; node_names: node index ->
+    name.  Text columns are left-aligned (`---`), numbers right-aligned (`---:`), as go-pretty writes them."""
+    cols = sorted(plugin_columns.items(), key=lambda kv: kv[1])
+    lines = ["| " + " | ".join(["#", "Pod", "Node", "Score"] + [name for _, name in cols]) + " |",
+             "|" + " --- |" * 3 + " ---:|" * (1 + len(cols))]
+    for i, r in enumerate(rows):
+        cells = [str(i), pod_ref, str(node_names[int(r["node_idx"])]), str(int(r["total"]))]
+        cells += [str(int(r["plugin"][c])) for c, _ in cols]
+        lines.append("| " + " | ".join(cells) + " |")
+    return "\n".join(lines)
+
 
 def _slots(d: dict | None, absent=0) -> np.ndarray:
     out = np.full(abi.RES_MAX, absent, dtype=np.int64)
@@ -400,6 +429,14 @@ class Scheduler:
         if c["la_score"]:
             out[LOAD_AWARE] = la
         return out
+
+    def debug_scores(self, topn: int, pod: np.ndarray, pod_ref: str, node_names) -> str:
+        """--debug-scores N for one pod (frameworkext/debug.go:61-108): the top-N table, ranked and broken down per
+        plugin on the device (kg_debug_topn), rendered with the profile's enabled Score plugins as columns."""
+        rows, _ = self.engine.debug_topn(pod, topn)
+        c = self.config[0]
+        cols = {k: name for k, name in PLUGIN_COLUMNS.items() if c[_PLUGIN_SCORE_FIELD[k]]}
+        return render_debug_table(rows, cols, pod_ref, node_names)
 
     def schedule_pods(self, pods: np.ndarray):
         return self.engine.schedule(pods)
