@@ -36,6 +36,8 @@
  *                           elasticquota/plugin_helper.go:237-246) + min, as the Go GroupQuotaManager holds them.
  *   kg_debug_topn           frameworkext's --debug-scores table (frameworkext/debug.go:61-108): the N best nodes of one
  *                           pod with their total and one column per Score plugin, ranked on the device.
+ *   kg_pods_diagnose        framework.FitError of the pods kg_pods_schedule answers with -1 (NumAllNodes, the
+ *                           NodeToStatusMap reasons histogram, Diagnosis.UnschedulablePlugins), reduced on the device.
  *   kg_last_error           error text for the last failing call on this thread (maps to framework.NewStatus(Error,…)).
  *
  * Units follow the reference's getResourceValue (load_aware/helper.go:146-151): cpu-like resources in
@@ -851,11 +853,58 @@ typedef struct {
 int kg_debug_topn(kg_engine* e, const kg_pod* pod, int32_t topn, kg_topn_row* out_rows, int64_t* out_n_rows,
                   int64_t* out_feasible);
 
+/* (added within ABI 18: one function, one struct, kg_abi_struct_size(12); the ABI number is unchanged)
+ * framework.FitError of `n` pods in one call, reduced on the device: per pod NumAllNodes, the feasible count, the
+ * NodeToStatusMap reasons histogram ("0/N nodes are available: 750 Insufficient cpu, ...") and the nodes per
+ * first-failing plugin (Diagnosis.UnschedulablePlugins = the plugins with plugin_nodes > 0).  The counterpart of
+ * kg_debug_topn for the pods kg_pods_schedule answers with -1.
+ *   - Per-node status.  What RunFilterPlugins leaves in the NodeToStatusMap: the first enabled Filter plugin that fails,
+ *     in the profile's Filter order (the reference's config/manager/scheduler-config.yaml:65-70 after the upstream
+ *     v1.24 defaults): TaintToleration, NodeAffinity, NodeResourcesFit, LoadAwareScheduling, NodeNUMAResource,
+ *     DeviceShare, Reservation — with all of that plugin's reasons and none of the later plugins'.  NodeResourcesFit
+ *     reports every failing resource at once, as upstream fitsRequest does (KG_REJECT_FIT_PODS, _FIT_CPU, _FIT_MEMORY,
+ *     _FIT_OTHER; a pod with all-zero requests reports only _FIT_PODS).  Every other plugin has one bit:
+ *     KG_REJECT_TAINT, _NODE_AFFINITY, _LOADAWARE, _NUMA, _DEVICE, _RESERVATION.  KG_REJECT_RESERVATION covers both
+ *     Reservation Filter paths: the reserve-pod / operating-mode policy check, and "no reservation satisfies a pod that
+ *     requires one".  Mapping bits to Unschedulable / UnschedulableAndUnresolvable codes stays with the caller.
+ *   - State seen.  Each pod is evaluated exactly as kg_pods_schedule would evaluate it as the next pod — the clock and
+ *     expired-metric handling, the BeforePreFilter restore, NodeNUMAResource / DeviceShare on the restored node.  Every
+ *     pod of the call sees the same current state; nothing is assumed between the pods of one call.  Called right after
+ *     a -1 this is that cycle's FitError (an unschedulable pod leaves the state unchanged); for a pod that failed
+ *     earlier in a batch it is the diagnosis as of now, not as of its own cycle.
+ *   - No state change.  Nothing is assumed: the device state, the staged queue, the results buffers and the scheduling
+ *     pass's scratch are the same after the call as before it.
+ *   - out_node_status, when non-NULL: out_node_status[j * kg_engine_num_nodes(e) + i] is pod j's word for node slot i;
+ *     0 = feasible, KG_REJECT_INVALID_NODE alone = an invalid slot (deleted / never upserted).  This is the status map a
+ *     PostFilter receives, and the only n-sized copy of the call.  Invalid slots are counted nowhere in kg_fit_diag.
+ *   - Invariants.  feasible + sum(plugin_nodes) == num_all_nodes.  For each single-bit plugin plugin_nodes[k] ==
+ *     reason_nodes[its bit].  For NodeResourcesFit max(reason_nodes of bits 0, 1, 2, 7) <= plugin_nodes[KG_PL_FIT] <=
+ *     their sum.  reason_nodes of bits the profile cannot produce are 0.  feasible == 0 exactly when kg_pods_schedule of
+ *     that pod alone returns -1, for profiles without ElasticQuota.
+ *   - ElasticQuota admission is not consulted: it is a PreFilter that stays with the caller, as for kg_debug_topn.
+ *   - Errors.  KG_E_INVALID: a null e, pods or out_diag with n > 0, n < 0 or n > KG_DIAG_MAX_PODS, and every pod
+ *     validation error kg_pods_stage raises; the message names the pod's index in the batch.  KG_E_UNSUPPORTED, with a
+ *     message saying which: a PodTopologySpread / InterPodAffinity profile, an engine that shards nodes over ranks, and
+ *     the per-pod refusals of kg_debug_topn (device requests without DeviceShare, RDMA / FPGA requests next to
+ *     reservations that hold GPUs).  n == 0 returns KG_OK; on an empty table every pod gets an all-zero kg_fit_diag.
+ * One host-to-device copy of the pod records, one device-to-host copy of n * sizeof(kg_fit_diag); the status words are
+ * further copies only when asked for. */
+#define KG_DIAG_REASONS 32
+#define KG_DIAG_MAX_PODS 16384
+typedef struct {
+  int64_t num_all_nodes;                 /* valid node slots evaluated: FitError.NumAllNodes */
+  int64_t feasible;                      /* nodes every enabled Filter passed */
+  int64_t plugin_nodes[KG_PL_COLUMNS];   /* nodes whose status comes from plugin KG_PL_* (the first Filter that failed) */
+  int64_t reason_nodes[KG_DIAG_REASONS]; /* nodes whose status carries KG_REJECT_* bit b */
+} kg_fit_diag;
+int kg_pods_diagnose(kg_engine* e, const kg_pod* pods, int64_t n, kg_fit_diag* out_diag,
+                     int32_t* out_node_status /* nullable: n x kg_engine_num_nodes words */);
+
 const char* kg_last_error(void);
 int kg_abi_version(void);
 /* sizeof of the ABI structs (0 kg_config, 1 kg_node, 2 kg_node_metric, 3 kg_pod, 4 kg_stats, 5 kg_node_numa,
- * 6 kg_node_device, 7 kg_quota, 8 kg_node_reservations, 9 kg_pod_metric, 10 kg_node_predicates, 11 kg_topn_row) for
- * binding checks. */
+ * 6 kg_node_device, 7 kg_quota, 8 kg_node_reservations, 9 kg_pod_metric, 10 kg_node_predicates, 11 kg_topn_row,
+ * 12 kg_fit_diag) for binding checks. */
 int64_t kg_abi_struct_size(int which);
 
 #ifdef __cplusplus

@@ -215,9 +215,17 @@ PL_FIT, PL_LOADAWARE, PL_NUMA, PL_DEVICESHARE, PL_RESERVATION, PL_TAINT, PL_NODE
 PL_COLUMNS = 16  # KG_PL_COLUMNS
 TOPN_ROW_DTYPE = np.dtype([("node_idx", np.int32), ("nominated", np.int32), _i64("total"), _i64("plugin", PL_COLUMNS)])
 
+# (added within ABI 18) kg_pods_diagnose: one pod's framework.FitError counts.  plugin_nodes[KG_PL_*] = the nodes whose
+# status comes from that plugin (the first Filter that failed), reason_nodes[b] = the nodes whose status carries
+# KG_REJECT_* bit b
+DIAG_REASONS = 32  # KG_DIAG_REASONS
+DIAG_MAX_PODS = 16384  # KG_DIAG_MAX_PODS
+FIT_DIAG_DTYPE = np.dtype([_i64("num_all_nodes"), _i64("feasible"), _i64("plugin_nodes", PL_COLUMNS),
+                           _i64("reason_nodes", DIAG_REASONS)])
+
 STRUCT_DTYPES = {0: CONFIG_DTYPE, 1: NODE_DTYPE, 2: METRIC_DTYPE, 3: POD_DTYPE, 4: STATS_DTYPE, 5: NODE_NUMA_DTYPE,
                  6: NODE_DEVICE_DTYPE, 7: QUOTA_DTYPE, 8: NODE_RSV_DTYPE, 9: POD_METRIC_DTYPE, 10: NODE_PRED_DTYPE,
-                 11: TOPN_ROW_DTYPE}
+                 11: TOPN_ROW_DTYPE, 12: FIT_DIAG_DTYPE}
 
 # Every symbol include/koordgpu.h declares (tests check the library exports all of them).
 EXPORTED_SYMBOLS = (
@@ -236,7 +244,7 @@ EXPORTED_SYMBOLS = (
     "kg_loopback_destroy", "kg_engine_create_loopback", "kg_pods_unreserve", "kg_engine_set_clock",
     "kg_node_pods_metric_set", "kg_debug_numa_merge", "kg_pods_evaluate_reservation", "kg_nodes_predicates_upsert",
     "kg_engine_create_hosted", "kg_pods_filter_preemption", "kg_nodes_read_pod_groups",
-    "kg_pods_select_victims", "kg_debug_topn",
+    "kg_pods_select_victims", "kg_debug_topn", "kg_pods_diagnose",
 )
 
 # int (*kg_exchange_fn)(void* user, const void* send, void* recv, int64_t bytes)
@@ -332,6 +340,7 @@ def load_library(path: str | None = None):
         "kg_nodes_read_pod_groups": (i, [vp, vp, vp, vp, vp, vp]),
         "kg_nodes_predicates_upsert": (i, [vp, vp, vp, i64]),
         "kg_debug_topn": (i, [vp, vp, ctypes.c_int32, vp, vp, vp]),
+        "kg_pods_diagnose": (i, [vp, vp, i64, vp, vp]),
         "kg_engine_create_hosted": (i, [vp, i64, i, i, EXCHANGE_FN, vp, ctypes.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():

@@ -70,6 +70,15 @@ __device__ __forceinline__ bool defaults_filter(const NodePred& n, const DefPod&
   }
   return true;
 }
+// (kg_pods_diagnose) the same Filter with each plugin reporting for itself: both are evaluated and each ORs its own
+// bit (KG_REJECT_TAINT / KG_REJECT_NODE_AFFINITY) into rej.  The schedulers call the overload above.
+__device__ __forceinline__ bool defaults_filter(const NodePred& n, const DefPod& d, const DefParams& F, uint32_t& rej) {
+  DefParams Ft = F, Fa = F;
+  Ft.aff_filter = 0, Fa.taint_filter = 0;
+  const bool t = defaults_filter(n, d, Ft), a = defaults_filter(n, d, Fa);
+  rej |= (t ? 0u : (uint32_t)KG_REJECT_TAINT) | (a ? 0u : (uint32_t)KG_REJECT_NODE_AFFINITY);
+  return t && a;
+}
 
 // TaintToleration raw Score: PreferNoSchedule taints the pod does not tolerate
 __device__ __forceinline__ int32_t taint_raw(const NodePred& n, const DefPod& d) {

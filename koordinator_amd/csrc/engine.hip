@@ -3497,6 +3497,7 @@ __global__ void select_victims(DevTable T, const RsvNode* __restrict__ RN, const
 // Scatter of upserted device rows
 #include "xr_dev.h"
 #include "topn_dev.h"
+#include "diag_dev.h"
 
 template <typename Rec>
 __global__ void scatter_rows(Rec* __restrict__ dst, const Rec* __restrict__ src, const int32_t* __restrict__ idx,
@@ -3899,6 +3900,7 @@ struct kg_engine {
   DevBuf<RowDelta> deltas;
   DevBuf<int64_t> scratch64;
   DevBuf<uint64_t> topn_buf;   // kg_debug_topn's own scratch: values, partials, candidates, the pod, the rows
+  DevBuf<uint64_t> diag_buf;   // kg_pods_diagnose's own scratch: the pods, a chunk's partials and status words, the results
   DevBuf<int32_t> scratch32;
   std::vector<int64_t> h_static64;
   std::vector<int32_t> h_static32;
@@ -5722,6 +5724,7 @@ int64_t kg_abi_struct_size(int which) {
     case 9: return sizeof(kg_pod_metric);
     case 10: return sizeof(kg_node_predicates);
     case 11: return sizeof(kg_topn_row);
+    case 12: return sizeof(kg_fit_diag);
   }
   return -1;
 }
@@ -6241,6 +6244,7 @@ void kg_engine_destroy(kg_engine* e) {
   e->gzm.release();
   e->scratch64.release();
   e->topn_buf.release();
+  e->diag_buf.release();
   e->scratch32.release();
   e->uidx.release();
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -7556,6 +7560,46 @@ int kg_pods_evaluate_reservation(kg_engine* e, const kg_pod* pod, int64_t* out) 
   return 0;
 }
 
+// One pod evaluated outside the staged queue (kg_debug_topn, kg_pods_diagnose): every per-plugin record the per-node
+// body reads, decoded and checked as kg_pods_stage does, with the refusals of the cases that body does not cover.
+// `k` is the pod's index in the caller's batch (the decoders' messages name it).
+struct LonePod {
+  DevPod d;
+  int64_t rq[kAux];
+  RsvPod rp;
+  RsvSel rs;
+  DsPod dsp;
+  NumaPod np;
+  DefPod df;
+};
+static int decode_lone_pod(kg_engine* e, const kg_pod& pod, int64_t k, LonePod& o) {
+  if (int rc = decode_pod(e, pod, o.d)) return rc;
+  for (int q = 0; q < kAux; ++q) o.rq[q] = pod.requests[kAuxFirst + q];
+  if (int rc = decode_rsv_pod(pod, o.rp, o.rs, k)) return rc;
+  if (int rc = check_rsv_predicates(e, rsv_pred_top(o.rp, o.rs))) return rc;
+  if (o.rp.flags & RP_SEL) o.rp.aux = 0;  // the caller's scratch copy of the selector
+  o.dsp = DsPod{};
+  o.dsp.skip = 1;
+  if (e->ds_on) {
+    if (int rc = decode_ds_pod(pod, o.dsp)) return rc;
+    if ((o.dsp.xq[0] | o.dsp.xq[1]) != 0 && e->rsv_on && e->rgpu_nodes > 0)
+      return fail(KG_E_UNSUPPORTED, "RDMA / FPGA requests with reservations that hold GPUs keep the Go path");
+  } else {
+    for (int r = 0; r < KG_DEV_RES_MAX; ++r)
+      if (pod.device_requests[r] != 0 && e->cfg.fit_filter)
+        return fail(KG_E_UNSUPPORTED, "the pod requests devices; the profile has no DeviceShare");
+  }
+  o.np = NumaPod{};
+  if (e->numa_on)
+    if (int rc = decode_numa_pod(e->cfg, pod, o.np)) return rc;
+  o.df = DefPod{};
+  if (e->def_on) {
+    if (int rc = decode_def_pod(pod, o.df, k)) return rc;
+    if (int rc = check_pod_tables(e, pod)) return rc;
+  }
+  return 0;
+}
+
 // (ABI 18) the --debug-scores table of one pod, ranked on the device (topn_dev.h): evaluate → select → final → gather,
 // plain launches in stream order over e->topn_buf, then one copy of the header and `topn` rows.  The per-node body is
 // rsv_eval_node — the exact pass's, which also serves single-pod schedule calls of every profile — so the table is what
@@ -7572,34 +7616,15 @@ int kg_debug_topn(kg_engine* e, const kg_pod* pod, int32_t topn, kg_topn_row* ou
     return fail(KG_E_UNSUPPORTED, "kg_debug_topn: the engine shards nodes over %d ranks (a rank holds a part of the "
                 "table; use a one-rank or replica engine)", e->n_ranks);
   if (int rc = sync_static(e)) return rc;
-  DevPod d;
-  if (int rc = decode_pod(e, *pod, d)) return rc;
-  int64_t rq[kAux];
-  for (int q = 0; q < kAux; ++q) rq[q] = pod->requests[kAuxFirst + q];
-  RsvPod rp;
-  RsvSel rs;
-  if (int rc = decode_rsv_pod(*pod, rp, rs, 0)) return rc;
-  if (int rc = check_rsv_predicates(e, rsv_pred_top(rp, rs))) return rc;
-  if (rp.flags & RP_SEL) rp.aux = 0;  // the scratch copy below
-  DsPod dsp{};
-  dsp.skip = 1;
-  if (e->ds_on) {
-    if (int rc = decode_ds_pod(*pod, dsp)) return rc;
-    if ((dsp.xq[0] | dsp.xq[1]) != 0 && e->rsv_on && e->rgpu_nodes > 0)
-      return fail(KG_E_UNSUPPORTED, "RDMA / FPGA requests with reservations that hold GPUs keep the Go path");
-  } else {
-    for (int r = 0; r < KG_DEV_RES_MAX; ++r)
-      if (pod->device_requests[r] != 0 && e->cfg.fit_filter)
-        return fail(KG_E_UNSUPPORTED, "the pod requests devices; the profile has no DeviceShare");
-  }
-  NumaPod np{};
-  if (e->numa_on)
-    if (int rc = decode_numa_pod(e->cfg, *pod, np)) return rc;
-  DefPod df{};
-  if (e->def_on) {
-    if (int rc = decode_def_pod(*pod, df, 0)) return rc;
-    if (int rc = check_pod_tables(e, *pod)) return rc;
-  }
+  LonePod lp;
+  if (int rc = decode_lone_pod(e, *pod, 0, lp)) return rc;
+  const DevPod& d = lp.d;
+  const int64_t (&rq)[kAux] = lp.rq;
+  const RsvPod& rp = lp.rp;
+  const RsvSel& rs = lp.rs;
+  const DsPod& dsp = lp.dsp;
+  const NumaPod& np = lp.np;
+  const DefPod& df = lp.df;
   const int64_t n = e->n_nodes;
   *out_n_rows = 0;
   *out_feasible = 0;
@@ -7667,6 +7692,78 @@ int kg_debug_topn(kg_engine* e, const kg_pod* pod, int32_t topn, kg_topn_row* ou
   std::memcpy(out_rows, host.data() + kHdrWords, (size_t)h.n_rows * sizeof(kg_topn_row));
   *out_n_rows = h.n_rows;
   *out_feasible = h.feasible;
+  return 0;
+}
+
+// (added within ABI 18) framework.FitError of n pods, reduced on the device (diag_dev.h): per chunk of kDiagChunk pods
+// diag_eval → diag_final, plain launches in stream order over e->diag_buf; one copy of every pod's records in, one copy
+// of n kg_fit_diag out, the status words of a chunk only when asked for.  The per-node body is rsv_eval_node, as in
+// kg_debug_topn: the pods are evaluated as kg_pods_schedule would evaluate each as the next pod, and the scheduling
+// buffers (rsv_val, rsv_part, rsv_ws, numa_aff, the DeviceShare normalisation buffers, the staged queue and its
+// results) are neither read nor written.
+int kg_pods_diagnose(kg_engine* e, const kg_pod* pods, int64_t n_pods, kg_fit_diag* out_diag, int32_t* out_node_status) {
+  if (!e) return fail(KG_E_INVALID, "engine is NULL");
+  if (n_pods < 0 || n_pods > KG_DIAG_MAX_PODS)
+    return fail(KG_E_INVALID, "kg_pods_diagnose: %lld pods outside 0..%d per call", (long long)n_pods, KG_DIAG_MAX_PODS);
+  if (n_pods > 0 && (!pods || !out_diag)) return fail(KG_E_INVALID, "null argument");
+  if (e->grp_on)
+    return fail(KG_E_UNSUPPORTED, "kg_pods_diagnose: PodTopologySpread / InterPodAffinity need the pass's cluster-wide "
+                "reductions (the Go path builds their FitError)");
+  if (e->n_ranks > 1)
+    return fail(KG_E_UNSUPPORTED, "kg_pods_diagnose: the engine shards nodes over %d ranks (a rank holds a part of the "
+                "table; use a one-rank or replica engine)", e->n_ranks);
+  if (n_pods == 0) return 0;
+  if (int rc = sync_static(e)) return rc;
+  std::vector<DiagPod> hp((size_t)n_pods);  // lives until the stream is synchronised
+  for (int64_t k = 0; k < n_pods; ++k) {
+    LonePod lp;
+    if (int rc = decode_lone_pod(e, pods[k], k, lp)) {
+      const std::string why = g_err;
+      return fail(rc, "kg_pods_diagnose: pod %lld of the batch: %s", (long long)k, why.c_str());
+    }
+    DiagPod& q = hp[(size_t)k];
+    std::memset(&q, 0, sizeof(q));
+    q.pod = lp.d, q.rpod = lp.rp, q.sel = lp.rs, q.dpod = lp.dsp, q.npod = lp.np, q.df = lp.df;
+    std::memcpy(q.aux, lp.rq, sizeof(lp.rq));
+  }
+  const int64_t n = e->n_nodes;
+  std::memset(out_diag, 0, (size_t)n_pods * sizeof(kg_fit_diag));
+  if (n == 0) return 0;
+  const int64_t nb = (n + kRsvThreads - 1) / kRsvThreads;
+  constexpr int64_t kPodW = (int64_t)(sizeof(DiagPod) / 8), kOutW = (int64_t)(sizeof(kg_fit_diag) / 8);
+  static_assert(sizeof(kg_fit_diag) % 8 == 0, "diag scratch layout");
+  const int64_t chunk = std::min<int64_t>(n_pods, kDiagChunk);
+  // word offsets into the scratch: every pod's records and result, one chunk's partial rows and status words
+  const int64_t o_pods = 0, o_out = o_pods + n_pods * kPodW, o_part = o_out + n_pods * kOutW,
+                o_st = o_part + (chunk * nb * kDiagRow + 1) / 2,
+                words = o_st + (out_node_status ? (chunk * n + 1) / 2 : 0);
+  if (int rc = e->diag_buf.ensure((size_t)words)) return rc;
+  uint64_t* b = e->diag_buf.p;
+  DiagPod* gp = reinterpret_cast<DiagPod*>(b + o_pods);
+  kg_fit_diag* go = reinterpret_cast<kg_fit_diag*>(b + o_out);
+  uint32_t* gpart = reinterpret_cast<uint32_t*>(b + o_part);
+  int32_t* gst = out_node_status ? reinterpret_cast<int32_t*>(b + o_st) : nullptr;
+  HIP_TRY(hipMemcpyAsync(gp, hp.data(), (size_t)n_pods * sizeof(DiagPod), hipMemcpyHostToDevice, e->stream));
+  RsvExt X = rsv_ext(e);
+  X.aff = nullptr;  // no pass affinity store: this is not a scheduling pass
+  X.val2 = nullptr;
+  X.gpods = nullptr;
+  const uint32_t on = (e->ds_on ? DIAG_DS : 0u) | (e->numa_on ? DIAG_NUMA : 0u) | (e->def_on ? DIAG_DEF : 0u);
+  for (int64_t c0 = 0; c0 < n_pods; c0 += chunk) {
+    const int64_t cn = std::min<int64_t>(chunk, n_pods - c0);
+    // pod groups: as many as fill the device with node blocks alone when the table is large, one pod per block row
+    // when it is small (kDiagFillBlocks is a choice, not a measured optimum)
+    const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(cn, (kDiagFillBlocks + nb - 1) / nb));
+    diag_eval<<<dim3((unsigned)nb, (unsigned)gy), kRsvThreads, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, gp + c0,
+                                                                               (int)cn, n, e->P, e->RP, X, on, gpart, gst);
+    diag_final<<<(unsigned)cn, kDiagFinalThreads, 0, e->stream>>>(gpart, (int)nb, go + c0);
+    HIP_TRY(hipGetLastError());
+    if (gst)
+      HIP_TRY(hipMemcpyAsync(out_node_status + (size_t)c0 * (size_t)n, gst, (size_t)cn * (size_t)n * 4,
+                             hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(out_diag, go, (size_t)n_pods * sizeof(kg_fit_diag), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
   return 0;
 }
 

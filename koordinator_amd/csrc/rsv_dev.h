@@ -369,6 +369,25 @@ __device__ __forceinline__ int64_t dsr_slot_score(const DsNode& d, const DsInst&
   return dsr_score(dsr_view(d, in, c, s, restricted, 0u), in, P);
 }
 
+// (kg_pods_diagnose) What RunFilterPlugins leaves in the NodeToStatusMap for a node, from the KG_REJECT_* bits of every
+// plugin that fails on it: the first failing plugin in the profile's Filter order (TaintToleration → NodeAffinity →
+// NodeResourcesFit → LoadAwareScheduling → NodeNUMAResource → DeviceShare → Reservation) with all of its reasons and
+// none of the later plugins'.  rsv_eval_node's own order (defaults → Reservation policy → Fit + LoadAware → aux →
+// Reservation affinity → DeviceShare → NodeNUMAResource) is not the framework's, so with a status pointer it evaluates
+// every plugin and this picks.  Evaluating the later plugins after an earlier failure is safe: each is a pure function
+// of the restored row and the node's static / device / NUMA records, reads nothing an earlier Filter guards, and
+// kg_pods_evaluate_numa / _device already run them on rows that fail NodeResourcesFit.
+__device__ __forceinline__ uint32_t rsv_status(uint32_t fl) {
+  constexpr uint32_t kFit = KG_REJECT_FIT_PODS | KG_REJECT_FIT_CPU | KG_REJECT_FIT_MEMORY | KG_REJECT_FIT_OTHER;
+  if (fl & KG_REJECT_TAINT) return KG_REJECT_TAINT;
+  if (fl & KG_REJECT_NODE_AFFINITY) return KG_REJECT_NODE_AFFINITY;
+  if (fl & kFit) return fl & kFit;  // fitsRequest reports every insufficient resource; LoadAware's bit is dropped
+  if (fl & KG_REJECT_LOADAWARE) return KG_REJECT_LOADAWARE;
+  if (fl & KG_REJECT_NUMA) return KG_REJECT_NUMA;
+  if (fl & KG_REJECT_DEVICE) return KG_REJECT_DEVICE;
+  return fl & KG_REJECT_RESERVATION;
+}
+
 // kSlotsInRegs = false: the slot record is read where used (the wide exact pass, register-bound); kExt = false: no
 // reserve-pod / operating-mode / reservation-selector logic (the batched exact rounds; the host routes queues holding
 // such pods to the per-pod pass); kXF = false: no RDMA / FPGA evaluation and no reserved-cpus NodeNUMAResource Score
@@ -379,14 +398,23 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
                                                 const RsvPod& rp, const EvalParams& P, const RsvParams& RP,
                                                 const RsvExt& X, const DsPod* dp, const NumaPod* np = nullptr,
                                                 RsvDbg* dbg = nullptr, const int64_t* aux_req = nullptr,
-                                                const DefPod* df = nullptr) {
+                                                const DefPod* df = nullptr, uint32_t* st = nullptr) {
   RsvOut o{false, 0, 0, -1, 0x7fffffff, 0, 0, 0};
   NodePred npd{0, 0, 0, 0};
+  // (kg_pods_diagnose) st set: no return at the first failing Filter; `fl` collects the KG_REJECT_* bits of every plugin
+  // that fails and *st receives the framework's status (rsv_status).  The scheduling instantiations pass the constant
+  // nullptr: fl and its stores are dead code there.
+  uint32_t fl = 0;
   if (df) {  // TaintToleration / NodeAffinity Filter: node-static, so first
     npd = X.pred[i];
-    if (!dbg && !defaults_filter(npd, *df, X.DF)) return o;
+    if (st) defaults_filter(npd, *df, X.DF, fl);
+    else if (!dbg && !defaults_filter(npd, *df, X.DF)) return o;
   }
   Row r = load_row(T, i);
+  if (st && !(r.flags & F_VALID)) {  // a deleted / never-upserted slot: its columns are not evaluated
+    *st = KG_REJECT_INVALID_NODE;
+    return o;
+  }
   const int ns = rsv_n[i];
   uint32_t mm = 0;  // matched slots
   uint32_t um = 0;  // unmatched slots with assigned pods (the restore's unmatched list)
@@ -415,17 +443,27 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
   // Reservation.Filter of a reserve pod / a pod in reservation operating mode (plugin.go:324-350): the reservation's
   // node, and no available reservation whose allocate policy conflicts (Default coexists with no other policy)
   if (kExt && RP.filter && (rp.flags & (RP_RESERVE | RP_OPERATING))) {
-    if ((rp.flags & RP_RESERVE) && rp.aux >= 0 && i != rp.aux) return o;
+    if ((rp.flags & RP_RESERVE) && rp.aux >= 0 && i != rp.aux) {
+      if (!st) return o;
+      fl |= KG_REJECT_RESERVATION;
+    }
     const int32_t pol = (int32_t)((rp.flags >> RP_POLICY_SHIFT) & 3);
 #pragma unroll
     for (int s = 0; s < kRsvSlots; ++s) {
       if (s >= ns || !(rn.meta[s] & RS_AVAIL)) continue;
       const int32_t ps = (int32_t)((rn.meta[s] >> 4) & 3);
-      if ((pol == KG_RSV_POLICY_DEFAULT || ps == KG_RSV_POLICY_DEFAULT) && pol != ps) return o;
+      if ((pol == KG_RSV_POLICY_DEFAULT || ps == KG_RSV_POLICY_DEFAULT) && pol != ps) {
+        if (!st) return o;
+        fl |= KG_REJECT_RESERVATION;
+      }
     }
   }
   int64_t t = 0;
-  if (dbg) {  // the same call with the two plugins' Scores reported
+  if (st) {  // every NodeResourcesFit reason and LoadAware's, as kg_pods_evaluate reports them
+    uint32_t rej = 0;
+    eval_node(r, p, P, t, &rej);
+    fl |= rej;
+  } else if (dbg) {  // the same call with the two plugins' Scores reported
     int64_t fs = 0, ls = 0;
     const bool ok = eval_node(r, p, P, t, nullptr, &fs, &ls);
     dbg->w_fit = P.fit_score ? fs * P.weight_fit : 0;
@@ -433,7 +471,10 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
     if (!ok) return o;
   } else if (!eval_node(r, p, P, t)) return o;  // NodeResourcesFit + LoadAware on the restored NodeInfo
   // fitsRequest over ephemeral-storage and the scalar resources the pod requests (reservation/plugin.go:469-479)
-  if (aux_req && P.fit_filter && !aux_fits(T, i, aux_req)) return o;
+  if (aux_req && P.fit_filter && !aux_fits(T, i, aux_req)) {
+    if (!st) return o;
+    fl |= KG_REJECT_FIT_OTHER;
+  }
   // satisfied(s): filterWithReservations([s]) (plugin.go:384-428) with fitsNode (:433-482), preemptible = 0
   const bool kc = (p.flags & P_CPU_KEY) != 0, km = (p.flags & P_MEM_KEY) != 0;
   uint32_t sat = 0;
@@ -454,7 +495,10 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
     }
   }
   // plugin.go:361-364, 423-426 (a reserve pod skips this part of the Filter, :357)
-  if (RP.filter && (rp.flags & RP_AFFINITY) && !(kExt && (rp.flags & RP_RESERVE)) && sat == 0) return o;
+  if (RP.filter && (rp.flags & RP_AFFINITY) && !(kExt && (rp.flags & RP_RESERVE)) && sat == 0) {
+    if (!st) return o;
+    fl |= KG_REJECT_RESERVATION;
+  }
   int64_t dsraw = 0;
   // (ABI 13) DeviceShare with the node's GPU-holding reservations (reservation.go, plugin.go:280-330): dsr = the
   // plugin keeps a restore state here; dsok = the GPU-holding matched slots it can allocate from (FilterReservation)
@@ -470,10 +514,16 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
       for (int s = 0; s < kRsvSlots; ++s) gslots |= (s < ns && (rn.meta[s] & RS_GPU)) ? (1u << s) : 0u;
     dsr = (gslots & (mm | um)) != 0 && !dp->error && d.has_device;
     if (!dsr) {  // the node-level Filter + raw Score
-      if (!ds_eval(d, *dp, X.DP, dsraw)) return o;
+      if (!ds_eval(d, *dp, X.DP, dsraw)) {
+        if (!st) return o;
+        fl |= KG_REJECT_DEVICE;
+      }
     } else {
       din = ds_instance(d, *dp);
-      if (!din.ok) return o;
+      if (!din.ok) {  // (st set: the slot checks below run on the empty instance; they can only repeat the same bit)
+        if (!st) return o;
+        fl |= KG_REJECT_DEVICE;
+      }
       dc = DsrCtx{X.rgpu + (size_t)i * kRsvSlots, um & gslots, mm & gslots};
 #pragma unroll
       for (int s = 0; s < kRsvSlots; ++s)
@@ -487,7 +537,10 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
         const DsrView v = dsr_view(d, din, dc, -1, false, 0u);
         pass = v.any && v.nfit >= din.count;
       }
-      if (X.DP.filter && !pass) return o;
+      if (X.DP.filter && !pass) {
+        if (!st) return o;
+        fl |= KG_REJECT_DEVICE;
+      }
     }
     // FilterReservation: a pod with device requests can use only a GPU-holding reservation DeviceShare can allocate
     // from (plugin.go:333-380: "no relevant Reservation information" for the others)
@@ -497,7 +550,10 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
     if constexpr (kExt && kXF) {
       if (X.dsx && (dp->xq[0] | dp->xq[1])) {
         int64_t xraw = 0;
-        if (!ds_eval_x(X.dsx[i], d.has_device != 0, *dp, X.DP, xraw)) return o;
+        if (!ds_eval_x(X.dsx[i], d.has_device != 0, *dp, X.DP, xraw)) {
+          if (!st) return o;
+          fl |= KG_REJECT_DEVICE;
+        }
         dsraw += xraw;
       }
     }
@@ -506,10 +562,18 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
   NumaHint naff{0, 1, 0, 0};
   if (kNuma && X.ns && np) {  // NodeNUMAResource Filter + Score on the restored NodeInfo; Reserve reuses the stored affinity
     const NumaView nv = make_view(X.ns + i, X.nm + i, X.NP);
-    if (!numa_eval(nv, *np, X.NP, r.req_cpu, r.req_mem, r.alloc_cpu, r.alloc_mem, nsc, naff)) return o;
+    if (!numa_eval(nv, *np, X.NP, r.req_cpu, r.req_mem, r.alloc_cpu, r.alloc_mem, nsc, naff)) {
+      if (!st) return o;
+      fl |= KG_REJECT_NUMA;
+    }
     if (X.NP.score) t += nsc * X.NP.weight;
     if (dbg && X.NP.score) dbg->w_numa = nsc * X.NP.weight;
     if (X.aff) X.aff[i] = naff.nil ? 0x100u : naff.mask;
+  }
+  if (st) {  // every Filter has run; the Scores and the nomination are the scheduler's business
+    *st = rsv_status(fl);
+    o.feas = fl == 0;
+    return o;
   }
   if (df) {  // BalancedAllocation on the restored NodeInfo; the two normalised raw Scores
     if (X.DF.bal) t += X.DF.w_bal * balanced_score(r.alloc_cpu, r.alloc_mem, r.req_cpu, r.req_mem, p.req_cpu, p.req_mem, X.DF);

@@ -447,6 +447,22 @@ class Engine:
         check(self.lib, self.lib.kg_debug_topn(self.h, ptr(pod), int(topn), ptr(out), ptr(counts[0:1]), ptr(counts[1:2])))
         return out[:int(counts[0])], int(counts[1])
 
+    def diagnose(self, pods: np.ndarray, node_status: bool = False):
+        """(added within ABI 18) kg_pods_diagnose: framework.FitError of `pods`, reduced on the device.  Returns an
+        abi.FIT_DIAG_DTYPE array, one record per pod: num_all_nodes, feasible, plugin_nodes[abi.PL_*] (the nodes whose
+        status comes from that plugin: the first Filter that failed, in the profile's Filter order) and
+        reason_nodes[b] (the nodes whose status carries abi.REJECT_* bit b).  Every pod is evaluated as the next pod
+        against the same current state; nothing is assumed and the engine's state is unchanged.  With node_status also
+        the (len(pods), num_nodes) int32 matrix of the per-node words (0 = feasible, abi.REJECT_INVALID_NODE alone = an
+        invalid slot): the NodeToStatusMap a PostFilter receives, and the only n-sized copy."""
+        pods = np.ascontiguousarray(np.asarray(pods, dtype=abi.POD_DTYPE).reshape(-1))
+        n = len(pods)
+        out = np.zeros(max(n, 1), dtype=abi.FIT_DIAG_DTYPE)
+        status = np.zeros((n, self.num_nodes), dtype=np.int32) if node_status else None
+        check(self.lib, self.lib.kg_pods_diagnose(self.h, ptr(pods) if n else None, n, ptr(out),
+                                                  ptr(status) if node_status and status.size else None))
+        return (out[:n], status) if node_status else out[:n]
+
     def debug_numa_merge(self, cases: np.ndarray) -> np.ndarray:
         """The device topology-manager policy merge on int64[n, DBG_MERGE_WORDS] cases (kg_debug_numa_merge);
         returns int64[n, 8]: admit, nil, mask, preferred, score."""

@@ -49,6 +49,51 @@ _PLUGIN_SCORE_FIELD = {
     abi.PL_BALANCED: "balanced_score", abi.PL_IMAGE_LOCALITY: "image_score",
 }
 
+# (kg_pods_diagnose) KG_REJECT_* bit -> the reason string FitError.Error() counts.  NodeResourcesFit's are upstream's
+# texts (noderesources/fit.go).  Where the reference's message carries a parameter the engine's bit does not (LoadAware's
+# "node(s) %s usage exceed threshold", the untolerated taint's key and value, the insufficient scalar resource's name,
+# NodeNUMAResource's / DeviceShare's / Reservation's several causes) there is one fixed class string per bit: these are
+# the engine's reason classes, not byte-equal to the Go messages.
+REASON_STRINGS = {
+    abi.REJECT_FIT_PODS: "Too many pods",
+    abi.REJECT_FIT_CPU: "Insufficient cpu",
+    abi.REJECT_FIT_MEMORY: "Insufficient memory",
+    abi.REJECT_FIT_OTHER: "Insufficient ephemeral-storage or scalar resource",
+    abi.REJECT_LOADAWARE: "node(s) usage exceed threshold",
+    abi.REJECT_NUMA: "node(s) NUMA topology or cpuset unsatisfied",
+    abi.REJECT_DEVICE: "Insufficient devices",
+    abi.REJECT_RESERVATION: "node(s) no reservation satisfies the pod or reservation policy conflict",
+    abi.REJECT_TAINT: "node(s) had untolerated taint",
+    abi.REJECT_NODE_AFFINITY: "node(s) didn't match Pod's node affinity/selector",
+}
+
+
+@dataclass(frozen=True)
+class FitError:
+    """framework.FitError of one pod as kg_pods_diagnose counts it: NumAllNodes, the feasible nodes, the NodeToStatusMap
+    reasons histogram and Diagnosis.UnschedulablePlugins (the plugins some node's status comes from).  `reasons` maps
+    REASON_STRINGS texts to node counts: the engine's reason classes, not byte-equal to the Go messages where those
+    carry a parameter.  message() follows upstream v1.24 FitError.Error(); upstream is not vendored in the reference
+    tree, so its exact text is parity-unpinned like the other upstream pieces."""
+    num_all_nodes: int
+    feasible_nodes: int
+    reasons: dict
+    unschedulable_plugins: frozenset
+
+    @classmethod
+    def from_diag(cls, diag) -> "FitError":
+        """From one abi.FIT_DIAG_DTYPE record (or a mapping with the same fields)."""
+        reasons = {text: int(diag["reason_nodes"][bit.bit_length() - 1]) for bit, text in REASON_STRINGS.items()
+                   if int(diag["reason_nodes"][bit.bit_length() - 1]) > 0}
+        plugins = frozenset(name for k, name in PLUGIN_COLUMNS.items() if int(diag["plugin_nodes"][k]) > 0)
+        return cls(int(diag["num_all_nodes"]), int(diag["feasible"]), reasons, plugins)
+
+    def message(self) -> str:
+        """`0/N nodes are available: ` + the "count reason" strings sorted as strings, joined by ", " + `.`
+        (scheduler/framework/types.go FitError.Error(), v1.24); reasons with a zero count are left out."""
+        parts = sorted(f"{int(v)} {k}" for k, v in self.reasons.items() if int(v) > 0)
+        return f"0/{self.num_all_nodes} nodes are available: " + ", ".join(parts) + "."
+
 
 def render_debug_table(rows, plugin_columns, pod_ref: str, node_names) -> str:
     """The Markdown table frameworkext's debugScores renders (frameworkext/debug.go:83-107, go-pretty RenderMarkdown):
@@ -437,6 +482,12 @@ class Scheduler:
         c = self.config[0]
         cols = {k: name for k, name in PLUGIN_COLUMNS.items() if c[_PLUGIN_SCORE_FIELD[k]]}
         return render_debug_table(rows, cols, pod_ref, node_names)
+
+    def fit_error(self, pod: np.ndarray) -> FitError:
+        """The FitError of a pod schedule_pod answered with -1, counted on the device (kg_pods_diagnose): call it right
+        after the -1 and it is that cycle's diagnosis (an unschedulable pod leaves the state unchanged).  The reason
+        strings are the engine's reason classes (REASON_STRINGS), not byte-equal to the Go messages."""
+        return FitError.from_diag(self.engine.diagnose(np.asarray(pod).reshape(1))[0])
 
     def schedule_pods(self, pods: np.ndarray):
         return self.engine.schedule(pods)
