@@ -38,6 +38,9 @@
  *                           pod with their total and one column per Score plugin, ranked on the device.
  *   kg_pods_diagnose        framework.FitError of the pods kg_pods_schedule answers with -1 (NumAllNodes, the
  *                           NodeToStatusMap reasons histogram, Diagnosis.UnschedulablePlugins), reduced on the device.
+ *   kg_pods_preempt         PostFilter's DryRunPreemption + SelectCandidate in one call: SelectVictimsOnNode for every
+ *                           candidate, then upstream's pickOneNodeForPreemption reduced on the device; one node and its
+ *                           victims come back.  kg_pods_pick_candidate: the pick alone, over results the caller holds.
  *   kg_last_error           error text for the last failing call on this thread (maps to framework.NewStatus(Error,…)).
  *
  * Units follow the reference's getResourceValue (load_aware/helper.go:146-151): cpu-like resources in
@@ -900,11 +903,67 @@ typedef struct {
 int kg_pods_diagnose(kg_engine* e, const kg_pod* pods, int64_t n, kg_fit_diag* out_diag,
                      int32_t* out_node_status /* nullable: n x kg_engine_num_nodes words */);
 
+/* (added within ABI 18: two functions, one struct, kg_abi_struct_size(13); the ABI number is unchanged)
+ * The preemption evaluator's SelectCandidate, reduced on the device: of the candidates of one dry run, the one node to
+ * preempt on and its victims — instead of a status word and a violating count per candidate and a byte per potential
+ * victim copied back for the host to walk.  Koordinator's evaluator asks for every node
+ * (elasticquota/preempt.go:43-45 GetOffsetAndNumCandidates returns (0, nodes)), so that copy is n-sized.
+ *   - The rule is upstream's, restated as published and NOT pinned by a reference table (the reference does not vendor
+ *     it): k8s.io/kubernetes v1.24 pkg/scheduler/framework/preemption/preemption.go SelectCandidate →
+ *     pickOneNodeForPreemption, and pkg/scheduler/util GetEarliestPodStartTime.  A candidate is eligible when its
+ *     dry-run status is 0; its victims are the entries of its segment with kept != 0, in the caller's reprieve order
+ *     (Victims.Pods: the kept PDB-violating victims first, then the kept others).  Among the eligible candidates:
+ *       0. a candidate with no victims left wins at once;
+ *       1. fewest numViolatingVictim;
+ *       2. lowest priority of the FIRST victim of the list (Victims.Pods[0]; not the maximum over the list);
+ *       3. lowest sum over the victims of int64(priority) + 2^31;
+ *       4. fewest victims;
+ *       5. the latest "earliest start time", the earliest start being taken among the victims that hold the true
+ *          maximum priority of the list;
+ *       6. what still ties goes to the lowest candidate position c (upstream iterates a Go map there; the lowest index
+ *          is this library's rule everywhere).
+ *     Each step narrows the set the previous one left.  No eligible candidate: candidate = node_idx = -1, the other
+ *     fields but `eligible` 0.  kg_pod carries neither PodPriority nor a start time: both arrive per victim.
+ *   - kg_pods_pick_candidate is the pick alone, over per-candidate results the caller holds — what a caller uses after
+ *     callExtenders has edited the candidates: reject[c], kept[k] and num_violating[c] as kg_pods_select_victims returns
+ *     them (out_reject, out_victim, out_violating), victim_priority[k] / victim_start_unix_nano[k] per entry of the
+ *     victims array.  node_idx[c] is only reported back (and checked against the table size).
+ *   - kg_pods_preempt is the dry run and the pick in one call: kg_pods_select_victims' kernel writes its outputs into
+ *     the call's device scratch, the pick reads them there, and only the pick comes back — plus, when out_reject is
+ *     non-NULL, the per-candidate status words (the FitError of a pod nobody can make room for needs those).
+ *     Arguments, profiles and refusals are those of kg_pods_select_victims.
+ *   - out_victims[0 .. out_pick->n_victims): the winner's victims as positions k into the victims array, in list order;
+ *     entries past n_victims are left untouched.  victims_cap = the entries out_victims holds; smaller than the longest
+ *     candidate segment is KG_E_INVALID (checked from the offsets before any launch).
+ *   - No state change: both calls use device scratch of their own; the device state, the staged queue, the results
+ *     buffers and every other call's scratch are the same after the call as before it.  n_candidates == 0 returns
+ *     KG_OK with candidate = -1.
+ * One device-to-host copy: the struct and the winner's positions. */
+typedef struct {
+  int64_t candidate;                /* position c in the call, -1 = none */
+  int64_t node_idx;                 /* node_idx[candidate], -1 = none */
+  int64_t eligible;                 /* candidates whose status was 0 */
+  int64_t n_victims;                /* victims of the winner */
+  int64_t num_violating;            /* its numViolatingVictim */
+  int64_t first_priority;           /* priority of its first victim (0 without victims) */
+  int64_t sum_priorities;           /* rule 3's sum: each victim's int64(priority) + 2^31 */
+  int64_t earliest_start_unix_nano; /* rule 5's earliest start among its highest-priority victims (0 without victims) */
+} kg_preempt_pick;
+int kg_pods_pick_candidate(kg_engine* e, int64_t n_candidates, const int32_t* node_idx, const int64_t* victim_offsets,
+                           const int32_t* reject, const uint8_t* kept, const int32_t* num_violating,
+                           const int32_t* victim_priority, const int64_t* victim_start_unix_nano,
+                           kg_preempt_pick* out_pick, int32_t* out_victims, int64_t victims_cap);
+int kg_pods_preempt(kg_engine* e, const kg_pod* pod, int64_t n_candidates, const int32_t* node_idx,
+                    const int64_t* victim_offsets, const kg_pod* victims, const int32_t* victim_slot,
+                    const int32_t* victim_minors, const uint8_t* pdb_violating, const int32_t* victim_priority,
+                    const int64_t* victim_start_unix_nano, kg_preempt_pick* out_pick, int32_t* out_victims,
+                    int64_t victims_cap, int32_t* out_reject /* nullable: n_candidates words */);
+
 const char* kg_last_error(void);
 int kg_abi_version(void);
 /* sizeof of the ABI structs (0 kg_config, 1 kg_node, 2 kg_node_metric, 3 kg_pod, 4 kg_stats, 5 kg_node_numa,
  * 6 kg_node_device, 7 kg_quota, 8 kg_node_reservations, 9 kg_pod_metric, 10 kg_node_predicates, 11 kg_topn_row,
- * 12 kg_fit_diag) for binding checks. */
+ * 12 kg_fit_diag, 13 kg_preempt_pick) for binding checks. */
 int64_t kg_abi_struct_size(int which);
 
 #ifdef __cplusplus

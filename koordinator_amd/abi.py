@@ -223,9 +223,16 @@ DIAG_MAX_PODS = 16384  # KG_DIAG_MAX_PODS
 FIT_DIAG_DTYPE = np.dtype([_i64("num_all_nodes"), _i64("feasible"), _i64("plugin_nodes", PL_COLUMNS),
                            _i64("reason_nodes", DIAG_REASONS)])
 
+# (added within ABI 18) kg_pods_pick_candidate / kg_pods_preempt: the candidate SelectCandidate picks.  candidate = its
+# position in the call (-1 = none), eligible = the candidates whose dry-run status was 0, sum_priorities = the sum of
+# each victim's int64(priority) + 2^31, earliest_start_unix_nano = the earliest start among its highest-priority victims
+PREEMPT_PICK_DTYPE = np.dtype([_i64("candidate"), _i64("node_idx"), _i64("eligible"), _i64("n_victims"),
+                               _i64("num_violating"), _i64("first_priority"), _i64("sum_priorities"),
+                               _i64("earliest_start_unix_nano")])
+
 STRUCT_DTYPES = {0: CONFIG_DTYPE, 1: NODE_DTYPE, 2: METRIC_DTYPE, 3: POD_DTYPE, 4: STATS_DTYPE, 5: NODE_NUMA_DTYPE,
                  6: NODE_DEVICE_DTYPE, 7: QUOTA_DTYPE, 8: NODE_RSV_DTYPE, 9: POD_METRIC_DTYPE, 10: NODE_PRED_DTYPE,
-                 11: TOPN_ROW_DTYPE, 12: FIT_DIAG_DTYPE}
+                 11: TOPN_ROW_DTYPE, 12: FIT_DIAG_DTYPE, 13: PREEMPT_PICK_DTYPE}
 
 # Every symbol include/koordgpu.h declares (tests check the library exports all of them).
 EXPORTED_SYMBOLS = (
@@ -244,7 +251,7 @@ EXPORTED_SYMBOLS = (
     "kg_loopback_destroy", "kg_engine_create_loopback", "kg_pods_unreserve", "kg_engine_set_clock",
     "kg_node_pods_metric_set", "kg_debug_numa_merge", "kg_pods_evaluate_reservation", "kg_nodes_predicates_upsert",
     "kg_engine_create_hosted", "kg_pods_filter_preemption", "kg_nodes_read_pod_groups",
-    "kg_pods_select_victims", "kg_debug_topn", "kg_pods_diagnose",
+    "kg_pods_select_victims", "kg_debug_topn", "kg_pods_diagnose", "kg_pods_pick_candidate", "kg_pods_preempt",
 )
 
 # int (*kg_exchange_fn)(void* user, const void* send, void* recv, int64_t bytes)
@@ -341,6 +348,8 @@ def load_library(path: str | None = None):
         "kg_nodes_predicates_upsert": (i, [vp, vp, vp, i64]),
         "kg_debug_topn": (i, [vp, vp, ctypes.c_int32, vp, vp, vp]),
         "kg_pods_diagnose": (i, [vp, vp, i64, vp, vp]),
+        "kg_pods_pick_candidate": (i, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
+        "kg_pods_preempt": (i, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
         "kg_engine_create_hosted": (i, [vp, i64, i, i, EXCHANGE_FN, vp, ctypes.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():

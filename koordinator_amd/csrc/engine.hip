@@ -3498,6 +3498,7 @@ __global__ void select_victims(DevTable T, const RsvNode* __restrict__ RN, const
 #include "xr_dev.h"
 #include "topn_dev.h"
 #include "diag_dev.h"
+#include "pick_dev.h"
 
 template <typename Rec>
 __global__ void scatter_rows(Rec* __restrict__ dst, const Rec* __restrict__ src, const int32_t* __restrict__ idx,
@@ -3901,6 +3902,7 @@ struct kg_engine {
   DevBuf<int64_t> scratch64;
   DevBuf<uint64_t> topn_buf;   // kg_debug_topn's own scratch: values, partials, candidates, the pod, the rows
   DevBuf<uint64_t> diag_buf;   // kg_pods_diagnose's own scratch: the pods, a chunk's partials and status words, the results
+  DevBuf<int64_t> pick_buf;    // kg_pods_pick_candidate's / kg_pods_preempt's own scratch: the call's arrays, keys, partials, the pick
   DevBuf<int32_t> scratch32;
   std::vector<int64_t> h_static64;
   std::vector<int32_t> h_static32;
@@ -5725,6 +5727,7 @@ int64_t kg_abi_struct_size(int which) {
     case 10: return sizeof(kg_node_predicates);
     case 11: return sizeof(kg_topn_row);
     case 12: return sizeof(kg_fit_diag);
+    case 13: return sizeof(kg_preempt_pick);
   }
   return -1;
 }
@@ -6245,6 +6248,7 @@ void kg_engine_destroy(kg_engine* e) {
   e->scratch64.release();
   e->topn_buf.release();
   e->diag_buf.release();
+  e->pick_buf.release();
   e->scratch32.release();
   e->uidx.release();
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -7869,6 +7873,82 @@ int kg_pods_filter_preemption(kg_engine* e, const kg_pod* pod, int32_t node_idx,
   return 0;
 }
 
+// the candidates of one dry-run call, checked (kg_pods_select_victims, kg_pods_preempt, kg_pods_pick_candidate): node
+// indices inside the table, offsets from 0 and non-decreasing.  nv = the victims in all, max_seg = the longest segment.
+static int candidates_check(kg_engine* e, int64_t n_candidates, const int32_t* node_idx, const int64_t* victim_offsets,
+                            int64_t& nv, int64_t& max_seg) {
+  if (victim_offsets[0] != 0) return fail(KG_E_INVALID, "victim_offsets[0] must be 0");
+  max_seg = 0;
+  for (int64_t c = 0; c < n_candidates; ++c) {
+    if (node_idx[c] < 0 || node_idx[c] >= e->n_nodes)
+      return fail(KG_E_INVALID, "candidate %lld: node index %d outside [0, %lld)", (long long)c, node_idx[c],
+                  (long long)e->n_nodes);
+    if (victim_offsets[c + 1] < victim_offsets[c])
+      return fail(KG_E_INVALID, "victim_offsets decrease at candidate %lld", (long long)c);
+    max_seg = std::max(max_seg, victim_offsets[c + 1] - victim_offsets[c]);
+  }
+  nv = victim_offsets[n_candidates];
+  return 0;
+}
+
+// word offsets of one dry-run call's device buffer: pod, pod aux, RsvSel, victims, offsets, nodes, violating flags, then
+// the outputs; `end` = the first word behind them
+struct DryRunLayout {
+  size_t o_pod, o_aux, o_sel, o_vic, o_off, o_nodes, o_viol, o_rej, o_out, o_nvio, end;
+};
+
+// uploads one dry-run call into `buf` (grown to the layout plus `tail` words for the caller) and launches select_victims
+// over it on the engine stream; the outputs stay on the device
+static int dry_run_launch(kg_engine* e, DevBuf<int64_t>& buf, size_t tail, int64_t n_candidates, const int32_t* node_idx,
+                          const int64_t* victim_offsets, int64_t nv, const uint8_t* pdb_violating, const DevPod& d,
+                          const RsvPod& rp, const RsvSel& rs, const int64_t (&rq)[kAux], const std::vector<Victim>& hv,
+                          const PreExt& X, DryRunLayout& L) {
+  auto words = [](size_t bytes) { return (bytes + 7) / 8; };
+  const size_t w_pod = kPodWords, w_aux = kAux, w_sel = words(sizeof(RsvSel)), w_vic = words(hv.size() * sizeof(Victim));
+  const size_t w_off = (size_t)n_candidates + 1, w_nodes = words((size_t)n_candidates * 4),
+               w_viol = words((size_t)std::max<int64_t>(nv, 1)), w_rej = words((size_t)n_candidates * 4),
+               w_out = words((size_t)std::max<int64_t>(nv, 1)), w_nvio = words((size_t)n_candidates * 4);
+  size_t o = 0;
+  L.o_pod = o; o += w_pod;
+  L.o_aux = o; o += w_aux;
+  L.o_sel = o; o += w_sel;
+  L.o_vic = o; o += w_vic;
+  L.o_off = o; o += w_off;
+  L.o_nodes = o; o += w_nodes;
+  L.o_viol = o; o += w_viol;
+  L.o_rej = o; o += w_rej;
+  L.o_out = o; o += w_out;
+  L.o_nvio = o; o += w_nvio;
+  L.end = o;
+  if (int rc = buf.ensure(o + tail)) return rc;
+  int64_t* b = buf.p;
+  HIP_TRY(hipMemcpyAsync(b + L.o_pod, &d, sizeof(d), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b + L.o_aux, rq, sizeof(rq), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b + L.o_sel, &rs, sizeof(rs), hipMemcpyHostToDevice, e->stream));
+  if (nv > 0) HIP_TRY(hipMemcpyAsync(b + L.o_vic, hv.data(), (size_t)nv * sizeof(Victim), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b + L.o_off, victim_offsets, w_off * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b + L.o_nodes, node_idx, (size_t)n_candidates * 4, hipMemcpyHostToDevice, e->stream));
+  const uint8_t* gviol = nullptr;
+  if (pdb_violating && nv > 0) {
+    HIP_TRY(hipMemcpyAsync(b + L.o_viol, pdb_violating, (size_t)nv, hipMemcpyHostToDevice, e->stream));
+    gviol = reinterpret_cast<const uint8_t*>(b + L.o_viol);
+  }
+  const unsigned blocks = (unsigned)((n_candidates + kWave - 1) / kWave);
+  select_victims<<<blocks, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, e->rsv_pd.p,
+                                                  reinterpret_cast<const RsvSel*>(b + L.o_sel),
+                                                  reinterpret_cast<const DevPod*>(b + L.o_pod),
+                                                  reinterpret_cast<const int64_t*>(b + L.o_aux), rp, e->P, e->RP,
+                                                  e->rsv_on ? 1 : 0, n_candidates,
+                                                  reinterpret_cast<const int32_t*>(b + L.o_nodes),
+                                                  reinterpret_cast<const int64_t*>(b + L.o_off),
+                                                  reinterpret_cast<const Victim*>(b + L.o_vic), gviol,
+                                                  reinterpret_cast<int32_t*>(b + L.o_rej),
+                                                  reinterpret_cast<uint8_t*>(b + L.o_out),
+                                                  reinterpret_cast<int32_t*>(b + L.o_nvio), X);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 int kg_pods_select_victims(kg_engine* e, const kg_pod* pod, int64_t n_candidates, const int32_t* node_idx,
                            const int64_t* victim_offsets, const kg_pod* victims, const int32_t* victim_slot,
                            const int32_t* victim_minors, const uint8_t* pdb_violating, int32_t* out_reject, uint8_t* out_victim,
@@ -7877,15 +7957,8 @@ int kg_pods_select_victims(kg_engine* e, const kg_pod* pod, int64_t n_candidates
                                                               !out_violating)))
     return fail(KG_E_INVALID, "null argument");
   if (n_candidates == 0) return 0;
-  if (victim_offsets[0] != 0) return fail(KG_E_INVALID, "victim_offsets[0] must be 0");
-  for (int64_t c = 0; c < n_candidates; ++c) {
-    if (node_idx[c] < 0 || node_idx[c] >= e->n_nodes)
-      return fail(KG_E_INVALID, "candidate %lld: node index %d outside [0, %lld)", (long long)c, node_idx[c],
-                  (long long)e->n_nodes);
-    if (victim_offsets[c + 1] < victim_offsets[c])
-      return fail(KG_E_INVALID, "victim_offsets decrease at candidate %lld", (long long)c);
-  }
-  const int64_t nv = victim_offsets[n_candidates];
+  int64_t nv, max_seg;
+  if (int rc = candidates_check(e, n_candidates, node_idx, victim_offsets, nv, max_seg)) return rc;
   if (nv > 0 && (!victims || !out_victim)) return fail(KG_E_INVALID, "null argument");
   DevPod d;
   RsvPod rp;
@@ -7894,54 +7967,156 @@ int kg_pods_select_victims(kg_engine* e, const kg_pod* pod, int64_t n_candidates
   std::vector<Victim> hv;
   PreExt X;
   if (int rc = preempt_prepare(e, pod, victims, victim_slot, victim_minors, nv, d, rp, rs, rq, hv, X)) return rc;
-  // one device buffer: pod, pod aux, RsvSel, victims, offsets, nodes, violating flags, then the outputs
-  auto words = [](size_t bytes) { return (bytes + 7) / 8; };
-  const size_t w_pod = kPodWords, w_aux = kAux, w_sel = words(sizeof(RsvSel)), w_vic = words(hv.size() * sizeof(Victim));
-  const size_t w_off = (size_t)n_candidates + 1, w_nodes = words((size_t)n_candidates * 4),
-               w_viol = words((size_t)std::max<int64_t>(nv, 1)), w_rej = words((size_t)n_candidates * 4),
-               w_out = words((size_t)std::max<int64_t>(nv, 1)), w_nvio = words((size_t)n_candidates * 4);
-  size_t o = 0;
-  const size_t o_pod = o; o += w_pod;
-  const size_t o_aux = o; o += w_aux;
-  const size_t o_sel = o; o += w_sel;
-  const size_t o_vic = o; o += w_vic;
-  const size_t o_off = o; o += w_off;
-  const size_t o_nodes = o; o += w_nodes;
-  const size_t o_viol = o; o += w_viol;
-  const size_t o_rej = o; o += w_rej;
-  const size_t o_out = o; o += w_out;
-  const size_t o_nvio = o; o += w_nvio;
-  if (int rc = e->scratch64.ensure(o)) return rc;
-  int64_t* b = e->scratch64.p;
-  HIP_TRY(hipMemcpyAsync(b + o_pod, &d, sizeof(d), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + o_aux, rq, sizeof(rq), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + o_sel, &rs, sizeof(rs), hipMemcpyHostToDevice, e->stream));
-  if (nv > 0) HIP_TRY(hipMemcpyAsync(b + o_vic, hv.data(), (size_t)nv * sizeof(Victim), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + o_off, victim_offsets, w_off * 8, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + o_nodes, node_idx, (size_t)n_candidates * 4, hipMemcpyHostToDevice, e->stream));
-  const uint8_t* gviol = nullptr;
-  if (pdb_violating && nv > 0) {
-    HIP_TRY(hipMemcpyAsync(b + o_viol, pdb_violating, (size_t)nv, hipMemcpyHostToDevice, e->stream));
-    gviol = reinterpret_cast<const uint8_t*>(b + o_viol);
-  }
-  const unsigned blocks = (unsigned)((n_candidates + kWave - 1) / kWave);
-  select_victims<<<blocks, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, e->rsv_pd.p,
-                                                  reinterpret_cast<const RsvSel*>(b + o_sel),
-                                                  reinterpret_cast<const DevPod*>(b + o_pod),
-                                                  reinterpret_cast<const int64_t*>(b + o_aux), rp, e->P, e->RP,
-                                                  e->rsv_on ? 1 : 0, n_candidates,
-                                                  reinterpret_cast<const int32_t*>(b + o_nodes),
-                                                  reinterpret_cast<const int64_t*>(b + o_off),
-                                                  reinterpret_cast<const Victim*>(b + o_vic), gviol,
-                                                  reinterpret_cast<int32_t*>(b + o_rej),
-                                                  reinterpret_cast<uint8_t*>(b + o_out),
-                                                  reinterpret_cast<int32_t*>(b + o_nvio), X);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out_reject, b + o_rej, (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(out_violating, b + o_nvio, (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
-  if (nv > 0) HIP_TRY(hipMemcpyAsync(out_victim, b + o_out, (size_t)nv, hipMemcpyDeviceToHost, e->stream));
+  DryRunLayout L;
+  if (int rc = dry_run_launch(e, e->scratch64, 0, n_candidates, node_idx, victim_offsets, nv, pdb_violating, d, rp, rs, rq,
+                              hv, X, L))
+    return rc;
+  const int64_t* b = e->scratch64.p;
+  HIP_TRY(hipMemcpyAsync(out_reject, b + L.o_rej, (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_violating, b + L.o_nvio, (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
+  if (nv > 0) HIP_TRY(hipMemcpyAsync(out_victim, b + L.o_out, (size_t)nv, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return 0;
+}
+
+// the pick's three launches (pick_dev.h) over one call's device arrays, then the one copy back: the header and the
+// winner's victim positions, of which there are at most max_seg
+struct PickDev {
+  const int32_t* nodes;
+  const int64_t* off;
+  const int32_t* rej;
+  const uint8_t* kept;
+  const int32_t* nvio;
+  const int32_t* prio;
+  const int64_t* start;
+  int64_t* tail;  // pick_tail_words(n_candidates, max_seg) words: keys, partials, the output
+};
+static size_t pick_tail_words(int64_t n_candidates, int64_t max_seg) {
+  return (size_t)n_candidates * (sizeof(PickKey) / 8) + (size_t)kPickBlocks * (sizeof(PickPart) / 8) +
+         sizeof(kg_preempt_pick) / 8 + (size_t)(max_seg + 1) / 2;
+}
+static int pick_run(kg_engine* e, int64_t n_candidates, int64_t max_seg, const PickDev& D, kg_preempt_pick* out_pick,
+                    int32_t* out_victims) {
+  static_assert(sizeof(PickKey) == 32 && sizeof(PickPart) == 40 && sizeof(kg_preempt_pick) == 64, "pick scratch layout");
+  PickKey* gkey = reinterpret_cast<PickKey*>(D.tail);
+  PickPart* gpart = reinterpret_cast<PickPart*>(D.tail + n_candidates * 4);
+  int64_t* gout = D.tail + n_candidates * 4 + kPickBlocks * 5;
+  kg_preempt_pick* ghdr = reinterpret_cast<kg_preempt_pick*>(gout);
+  int32_t* gvic = reinterpret_cast<int32_t*>(gout + 8);
+  const int64_t nb = (n_candidates + kPickWaves - 1) / kPickWaves;
+  const int np = (int)std::min<int64_t>((n_candidates + kPickThreads - 1) / kPickThreads, kPickBlocks);
+  pick_keys<<<(unsigned)nb, kPickThreads, 0, e->stream>>>(n_candidates, D.off, D.rej, D.kept, D.nvio, D.prio, D.start, gkey);
+  pick_reduce<<<(unsigned)np, kPickThreads, 0, e->stream>>>(gkey, n_candidates, gpart);
+  pick_final<<<1, kPickThreads, 0, e->stream>>>(gpart, np, D.nodes, D.off, D.kept, ghdr, gvic, max_seg);
+  HIP_TRY(hipGetLastError());
+  std::vector<int64_t> host(8 + (size_t)(max_seg + 1) / 2);
+  HIP_TRY(hipMemcpyAsync(host.data(), gout, host.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  kg_preempt_pick h;
+  std::memcpy(&h, host.data(), sizeof(h));
+  if (h.candidate < -1 || h.candidate >= n_candidates || h.n_victims < 0 || h.n_victims > max_seg)
+    return fail(KG_E_DEVICE, "preemption pick: candidate %lld with %lld victims", (long long)h.candidate,
+                (long long)h.n_victims);
+  *out_pick = h;
+  if (h.n_victims > 0) std::memcpy(out_victims, host.data() + 8, (size_t)h.n_victims * 4);
+  return 0;
+}
+static const kg_preempt_pick kPickNoCandidate = {-1, -1, 0, 0, 0, 0, 0, 0};
+
+// (added within ABI 18) SelectCandidate over per-candidate dry-run results the caller holds (pick_dev.h): seven copies
+// in, pick_keys → pick_reduce → pick_final in stream order over e->pick_buf, one copy out.  No engine state is read
+// beyond the table size the node indices are checked against; none is written.
+int kg_pods_pick_candidate(kg_engine* e, int64_t n_candidates, const int32_t* node_idx, const int64_t* victim_offsets,
+                           const int32_t* reject, const uint8_t* kept, const int32_t* num_violating,
+                           const int32_t* victim_priority, const int64_t* victim_start_unix_nano,
+                           kg_preempt_pick* out_pick, int32_t* out_victims, int64_t victims_cap) {
+  if (!e || !out_pick || n_candidates < 0 || victims_cap < 0 ||
+      (n_candidates > 0 && (!node_idx || !victim_offsets || !reject || !num_violating)))
+    return fail(KG_E_INVALID, "null argument");
+  *out_pick = kPickNoCandidate;
+  if (n_candidates == 0) return 0;
+  if (n_candidates > INT32_MAX) return fail(KG_E_INVALID, "kg_pods_pick_candidate: %lld candidates", (long long)n_candidates);
+  int64_t nv, max_seg;
+  if (int rc = candidates_check(e, n_candidates, node_idx, victim_offsets, nv, max_seg)) return rc;
+  if (nv > INT32_MAX) return fail(KG_E_INVALID, "kg_pods_pick_candidate: %lld victims (positions are int32)", (long long)nv);
+  if (nv > 0 && (!kept || !victim_priority || !victim_start_unix_nano)) return fail(KG_E_INVALID, "null argument");
+  if (victims_cap < max_seg)
+    return fail(KG_E_INVALID, "victims_cap %lld below the longest candidate segment %lld", (long long)victims_cap,
+                (long long)max_seg);
+  if (max_seg > 0 && !out_victims) return fail(KG_E_INVALID, "null argument");
+  for (int64_t c = 0; c < n_candidates; ++c)
+    if (num_violating[c] < 0)
+      return fail(KG_E_INVALID, "candidate %lld: num_violating %d", (long long)c, num_violating[c]);
+  auto words = [](size_t bytes) { return (bytes + 7) / 8; };
+  const size_t nc = (size_t)n_candidates, nvs = (size_t)std::max<int64_t>(nv, 1);
+  const size_t o_off = 0, o_nodes = o_off + nc + 1, o_rej = o_nodes + words(nc * 4), o_nvio = o_rej + words(nc * 4),
+               o_kept = o_nvio + words(nc * 4), o_prio = o_kept + words(nvs), o_start = o_prio + words(nvs * 4),
+               o_tail = o_start + nvs;
+  if (int rc = e->pick_buf.ensure(o_tail + pick_tail_words(n_candidates, max_seg))) return rc;
+  int64_t* b = e->pick_buf.p;
+  HIP_TRY(hipMemcpyAsync(b + o_off, victim_offsets, (nc + 1) * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b + o_nodes, node_idx, nc * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b + o_rej, reject, nc * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b + o_nvio, num_violating, nc * 4, hipMemcpyHostToDevice, e->stream));
+  if (nv > 0) {
+    HIP_TRY(hipMemcpyAsync(b + o_kept, kept, (size_t)nv, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(b + o_prio, victim_priority, (size_t)nv * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(b + o_start, victim_start_unix_nano, (size_t)nv * 8, hipMemcpyHostToDevice, e->stream));
+  }
+  const PickDev D{reinterpret_cast<const int32_t*>(b + o_nodes), b + o_off, reinterpret_cast<const int32_t*>(b + o_rej),
+                  reinterpret_cast<const uint8_t*>(b + o_kept), reinterpret_cast<const int32_t*>(b + o_nvio),
+                  reinterpret_cast<const int32_t*>(b + o_prio), b + o_start, b + o_tail};
+  return pick_run(e, n_candidates, max_seg, D, out_pick, out_victims);
+}
+
+// (added within ABI 18) the dry run and the pick in one call: select_victims — the kernel kg_pods_select_victims
+// launches, unchanged — writes its three outputs into e->pick_buf, the pick kernels read them there in stream order, and
+// only the pick comes back (plus the status words when asked for).  Refusals and argument checks are
+// kg_pods_select_victims', through the same preempt_prepare; the engine's scratch64 and state are not touched.
+int kg_pods_preempt(kg_engine* e, const kg_pod* pod, int64_t n_candidates, const int32_t* node_idx,
+                    const int64_t* victim_offsets, const kg_pod* victims, const int32_t* victim_slot,
+                    const int32_t* victim_minors, const uint8_t* pdb_violating, const int32_t* victim_priority,
+                    const int64_t* victim_start_unix_nano, kg_preempt_pick* out_pick, int32_t* out_victims,
+                    int64_t victims_cap, int32_t* out_reject) {
+  if (!e || !pod || !out_pick || n_candidates < 0 || victims_cap < 0 || (n_candidates > 0 && (!node_idx || !victim_offsets)))
+    return fail(KG_E_INVALID, "null argument");
+  *out_pick = kPickNoCandidate;
+  if (n_candidates == 0) return 0;
+  if (n_candidates > INT32_MAX) return fail(KG_E_INVALID, "kg_pods_preempt: %lld candidates", (long long)n_candidates);
+  int64_t nv, max_seg;
+  if (int rc = candidates_check(e, n_candidates, node_idx, victim_offsets, nv, max_seg)) return rc;
+  if (nv > INT32_MAX) return fail(KG_E_INVALID, "kg_pods_preempt: %lld victims (positions are int32)", (long long)nv);
+  if (nv > 0 && (!victims || !victim_priority || !victim_start_unix_nano)) return fail(KG_E_INVALID, "null argument");
+  if (victims_cap < max_seg)
+    return fail(KG_E_INVALID, "victims_cap %lld below the longest candidate segment %lld", (long long)victims_cap,
+                (long long)max_seg);
+  if (max_seg > 0 && !out_victims) return fail(KG_E_INVALID, "null argument");
+  DevPod d;
+  RsvPod rp;
+  RsvSel rs;
+  int64_t rq[kAux];
+  std::vector<Victim> hv;
+  PreExt X;
+  if (int rc = preempt_prepare(e, pod, victims, victim_slot, victim_minors, nv, d, rp, rs, rq, hv, X)) return rc;
+  auto words = [](size_t bytes) { return (bytes + 7) / 8; };
+  const size_t nvs = (size_t)std::max<int64_t>(nv, 1);
+  const size_t t_prio = 0, t_start = t_prio + words(nvs * 4), t_tail = t_start + nvs;
+  DryRunLayout L;
+  if (int rc = dry_run_launch(e, e->pick_buf, t_tail + pick_tail_words(n_candidates, max_seg), n_candidates, node_idx,
+                              victim_offsets, nv, pdb_violating, d, rp, rs, rq, hv, X, L))
+    return rc;
+  int64_t* b = e->pick_buf.p;
+  if (nv > 0) {
+    HIP_TRY(hipMemcpyAsync(b + L.end + t_prio, victim_priority, (size_t)nv * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(b + L.end + t_start, victim_start_unix_nano, (size_t)nv * 8, hipMemcpyHostToDevice, e->stream));
+  }
+  if (out_reject)
+    HIP_TRY(hipMemcpyAsync(out_reject, b + L.o_rej, (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
+  const PickDev D{reinterpret_cast<const int32_t*>(b + L.o_nodes), b + L.o_off,
+                  reinterpret_cast<const int32_t*>(b + L.o_rej), reinterpret_cast<const uint8_t*>(b + L.o_out),
+                  reinterpret_cast<const int32_t*>(b + L.o_nvio), reinterpret_cast<const int32_t*>(b + L.end + t_prio),
+                  b + L.end + t_start, b + L.end + t_tail};
+  return pick_run(e, n_candidates, max_seg, D, out_pick, out_victims);
 }
 
 int kg_results_fetch_reservations(kg_engine* e, int64_t first, int64_t count, int32_t* out_slot) {

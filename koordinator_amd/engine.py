@@ -419,6 +419,78 @@ class Engine:
         return (rej[:len(nodes)], [kept[off[c]:off[c + 1]].astype(bool) for c in range(len(nodes))],
                 nvio[:len(nodes)])
 
+    def pick_candidate(self, nodes, victim_offsets, reject, kept, num_violating, victim_priority, victim_start,
+                       victims_cap: int | None = None):
+        """(added within ABI 18) kg_pods_pick_candidate: upstream's SelectCandidate / pickOneNodeForPreemption reduced
+        on the device, over per-candidate dry-run results the caller holds (what select_victims returned, possibly
+        edited by extenders).  victim_offsets: int64[C + 1] into the flat per-victim arrays `kept` (uint8),
+        `victim_priority` (int32) and `victim_start` (int64 unix nanoseconds); reject / num_violating: int32[C].
+        Returns (pick, victims): one abi.PREEMPT_PICK_DTYPE record (candidate = -1: no eligible candidate) and the
+        winner's victims as int32 positions into the flat arrays, in list order.  victims_cap: the room for them
+        (default: the longest segment; smaller is refused).  The engine's state is unchanged."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        off = np.ascontiguousarray(victim_offsets, dtype=np.int64)
+        nc = len(nodes)
+        if len(off) != nc + 1:
+            raise ValueError("victim_offsets: one entry per candidate and the total")
+        rej = np.ascontiguousarray(reject, dtype=np.int32)
+        nvio = np.ascontiguousarray(num_violating, dtype=np.int32)
+        kp = np.ascontiguousarray(kept, dtype=np.uint8)
+        pr = np.ascontiguousarray(victim_priority, dtype=np.int32)
+        stt = np.ascontiguousarray(victim_start, dtype=np.int64)
+        nv = int(off[-1])
+        if len(rej) < nc or len(nvio) < nc or min(len(kp), len(pr), len(stt)) < nv:
+            raise ValueError("pick_candidate: an array is shorter than the candidates / victims it describes")
+        cap = int(np.diff(off).max(initial=0)) if victims_cap is None else int(victims_cap)
+        pick = np.zeros(1, dtype=abi.PREEMPT_PICK_DTYPE)
+        out = np.zeros(max(cap, 1), dtype=np.int32)
+        check(self.lib, self.lib.kg_pods_pick_candidate(self.h, nc, ptr(nodes), ptr(off), ptr(rej), ptr(kp), ptr(nvio),
+                                                        ptr(pr), ptr(stt), ptr(pick), ptr(out), cap))
+        return pick[0], out[:int(pick[0]["n_victims"])]
+
+    def preempt(self, pod: np.ndarray, nodes, victims_per_node, priorities_per_node, starts_per_node,
+                slots_per_node=None, violating_per_node=None, minors_per_node=None, want_reject: bool = False,
+                victims_cap: int | None = None):
+        """(added within ABI 18) kg_pods_preempt: the dry run of select_victims and SelectCandidate's pick in one call;
+        only the pick comes back.  victims_per_node / slots / violating / minors as for select_victims;
+        priorities_per_node[c] (int32) and starts_per_node[c] (int64 unix nanoseconds): PodPriority and the start time
+        of candidate c's potential victims.  Returns (pick, victims): one abi.PREEMPT_PICK_DTYPE record (candidate =
+        -1: nobody can make room) and the winner's victims as indices into victims_per_node[pick["candidate"]], in list
+        order; with want_reject also the int32[C] per-candidate status words.  The engine's state is unchanged."""
+        pod = np.ascontiguousarray(np.asarray(pod, dtype=abi.POD_DTYPE).reshape(1))
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        nc = len(nodes)
+        off = np.zeros(nc + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(v) for v in victims_per_node], dtype=np.int64)
+        nv = int(off[-1])
+
+        def flat(per_node, dtype):
+            if not nv:
+                return np.zeros(1, dtype=dtype)
+            # joined as bytes: numpy concatenates records field by field, ten times slower at 100k lists
+            parts = [np.ascontiguousarray(np.asarray(v, dtype=dtype).reshape(-1)).view(np.uint8) for v in per_node]
+            a = np.concatenate(parts).view(dtype)
+            if len(a) != nv:
+                raise ValueError("preempt: a per-victim list does not match its node's victims")
+            return a
+
+        vic = flat(victims_per_node, abi.POD_DTYPE)
+        pr = flat(priorities_per_node, np.int32)
+        stt = flat(starts_per_node, np.int64)
+        sl = flat(slots_per_node, np.int32) if slots_per_node is not None and nv else None
+        vio = flat(violating_per_node, np.uint8) if violating_per_node is not None and nv else None
+        mi = flat(minors_per_node, np.int32) if minors_per_node is not None and nv else None
+        cap = int(np.diff(off).max(initial=0)) if victims_cap is None else int(victims_cap)
+        pick = np.zeros(1, dtype=abi.PREEMPT_PICK_DTYPE)
+        out = np.zeros(max(cap, 1), dtype=np.int32)
+        rej = np.zeros(max(nc, 1), dtype=np.int32) if want_reject else None
+        check(self.lib, self.lib.kg_pods_preempt(self.h, ptr(pod), nc, ptr(nodes), ptr(off), ptr(vic), ptr(sl), ptr(mi),
+                                                 ptr(vio), ptr(pr), ptr(stt), ptr(pick), ptr(out), cap, ptr(rej)))
+        c = int(pick[0]["candidate"])
+        victims = out[:int(pick[0]["n_victims"])] - (off[c] if c >= 0 else 0)
+        victims = victims.astype(np.int32)
+        return (pick[0], victims, rej[:nc]) if want_reject else (pick[0], victims)
+
     def evaluate_reservation(self, pod: np.ndarray) -> dict:
         """The exact pass's evaluation of one pod on every node (kg_pods_evaluate_reservation): per node pass,
         nominated slot, raw Reservation score, restore state (has_state, matched slots, restored Requested /

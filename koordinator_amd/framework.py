@@ -489,6 +489,17 @@ class Scheduler:
         strings are the engine's reason classes (REASON_STRINGS), not byte-equal to the Go messages."""
         return FitError.from_diag(self.engine.diagnose(np.asarray(pod).reshape(1))[0])
 
+    def select_candidate(self, pod: np.ndarray, nodes, victims_per_node, priorities_per_node, starts_per_node, **kw):
+        """PostFilter's DryRunPreemption + SelectCandidate for the candidate nodes the caller chose (kg_pods_preempt;
+        arguments as Engine.preempt).  Returns (pick, victim pod records of the picked node in Victims.Pods order);
+        pick["candidate"] = -1 and no victims when nobody can make room.  The rule is upstream's
+        pickOneNodeForPreemption, ties on the lowest candidate position."""
+        pick, idx, *rest = self.engine.preempt(pod, nodes, victims_per_node, priorities_per_node, starts_per_node, **kw)
+        c = int(pick["candidate"])
+        pods = (np.asarray(victims_per_node[c], dtype=abi.POD_DTYPE).reshape(-1)[idx] if c >= 0
+                else np.zeros(0, dtype=abi.POD_DTYPE))
+        return (pick, pods, *rest)
+
     def schedule_pods(self, pods: np.ndarray):
         return self.engine.schedule(pods)
 
