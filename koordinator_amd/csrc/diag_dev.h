@@ -8,8 +8,8 @@
 //   diag_eval    one thread per node, blocks of kRsvThreads; grid (node blocks, pod groups).  A block loops over the
 //                pods of its group (pod j = blockIdx.y, += gridDim.y: with one group this is the plain pod loop, with as
 //                many groups as pods the 2-D grid; the host sizes the groups to fill the device).  The pod index is
-//                block-uniform, so the pod records come through scalar loads.  Per pod the thread runs rsv_eval_node —
-//                the scheduler's per-node body — with a status pointer, which makes it evaluate every Filter and report
+//                block-uniform, so the pod records (one LonePod per pod) come through scalar loads.  Per pod the
+//                thread runs rsv_eval_node — the scheduler's per-node body — with a status pointer, which makes it evaluate every Filter and report
 //                the framework's first failure (rsv_status).  Per counter one ballot + population count per wave; the
 //                waves combine through LDS (double-buffered by the loop's parity: one barrier per pod) and the block
 //                stores one partial row part[pod][block][kDiagRow].  With a status buffer each thread stores its word.
@@ -35,22 +35,9 @@ static_assert((1u << diag_bit(3)) == KG_REJECT_LOADAWARE && (1u << diag_bit(4)) 
               (1u << diag_bit(9)) == KG_REJECT_NODE_AFFINITY, "diag reason bits");
 static_assert(kDiagCnt <= kDiagRow && KG_DIAG_REASONS == 32, "diag row");
 
-// one pod of the call, in the call's scratch (not the staged queue's records); packed on the host
-struct DiagPod {
-  DevPod pod;
-  RsvPod rpod;          // RP_SEL: aux = 0, the selector is `sel`
-  RsvSel sel;
-  int64_t aux[kAux];    // read when pod.flags has P_AUX
-  DsPod dpod;           // read when DeviceShare is in the profile
-  NumaPod npod;         // read when NodeNUMAResource is in the profile
-  DefPod df;            // read when an upstream default plugin is in the profile
-};
-static_assert(sizeof(DiagPod) % 8 == 0, "DiagPod layout");
-constexpr uint32_t DIAG_DS = 1u, DIAG_NUMA = 2u, DIAG_DEF = 4u;
-
 __global__ __launch_bounds__(kRsvThreads) void diag_eval(DevTable T, const RsvNode* __restrict__ RN,
                                                          const int32_t* __restrict__ rsv_n,
-                                                         const DiagPod* __restrict__ pods, int n_pods, int64_t n,
+                                                         const LonePod* __restrict__ pods, int n_pods, int64_t n,
                                                          EvalParams P, RsvParams RP, RsvExt X, uint32_t on,
                                                          uint32_t* __restrict__ part, int32_t* __restrict__ status) {
   __shared__ uint32_t s_cnt[2][kRsvThreads / kWave][kDiagRow];
@@ -59,15 +46,12 @@ __global__ __launch_bounds__(kRsvThreads) void diag_eval(DevTable T, const RsvNo
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   int par = 0;
   for (int j = blockIdx.y; j < n_pods; j += gridDim.y, par ^= 1) {  // uniform over the block
-    const DiagPod& q = pods[j];
+    const LonePod& q = pods[j];
     uint32_t w = KG_REJECT_INVALID_NODE;  // rows past the table count nowhere, like invalid slots
     if (i < n) {
-      RsvExt Xj = X;
-      Xj.rsv_sel = &q.sel;
+      const LoneArgs a = lone_args(q, on, X);
       w = 0;
-      rsv_eval_node(T, RN, rsv_n, i, q.pod, q.rpod, P, RP, Xj, (on & DIAG_DS) ? &q.dpod : nullptr,
-                    (on & DIAG_NUMA) ? &q.npod : nullptr, nullptr, (q.pod.flags & P_AUX) ? q.aux : nullptr,
-                    (on & DIAG_DEF) ? &q.df : nullptr, &w);
+      rsv_eval_node(T, RN, rsv_n, i, q.pod, q.rpod, P, RP, a.X, a.dpod, a.npod, nullptr, a.aux, a.df, &w);
       if (status) status[(size_t)j * (size_t)n + (size_t)i] = (int32_t)w;
     }
     const bool valid = w != KG_REJECT_INVALID_NODE;

@@ -3155,16 +3155,47 @@ __global__ void evaluate_pod_ds(DsTable DT, const DsPod* __restrict__ pod, int64
   score[i] = ok ? raw : 0;
 }
 
+// One pod evaluated outside the staged queue (kg_pods_evaluate_reservation, kg_debug_topn, kg_pods_diagnose, the
+// preemption dry run): every per-plugin record the per-node body reads, in the call's scratch (not the staged queue's
+// records).  The host fills it (decode_lone_pod) and uploads it in one copy.
+struct LonePod {
+  DevPod pod;
+  RsvPod rpod;          // RP_SEL: aux = 0, the selector is `sel`
+  RsvSel sel;
+  int64_t aux[kAux];    // read when pod.flags has P_AUX
+  DsPod dpod;           // read when DeviceShare is in the profile
+  NumaPod npod;         // read when NodeNUMAResource is in the profile
+  DefPod df;            // read when an upstream default plugin is in the profile
+};
+static_assert(sizeof(LonePod) % 8 == 0, "LonePod layout");
+// which of a LonePod's records rsv_eval_node gets: LONE_DS / LONE_NUMA / LONE_DEF follow the profile, LONE_AUX is the
+// entry point's (with it, a P_AUX pod's ephemeral-storage / scalar requests are checked)
+constexpr uint32_t LONE_DS = 1u, LONE_NUMA = 2u, LONE_DEF = 4u, LONE_AUX = 8u;
+// rsv_eval_node's nullable pod arguments and its RsvExt (rsv_sel = the record's selector) for one LonePod
+struct LoneArgs {
+  const DsPod* dpod;
+  const NumaPod* npod;
+  const int64_t* aux;
+  const DefPod* df;
+  RsvExt X;
+};
+__device__ __forceinline__ LoneArgs lone_args(const LonePod& q, uint32_t on, const RsvExt& X) {
+  LoneArgs a{(on & LONE_DS) ? &q.dpod : nullptr, (on & LONE_NUMA) ? &q.npod : nullptr,
+             ((on & LONE_AUX) && (q.pod.flags & P_AUX)) ? q.aux : nullptr, (on & LONE_DEF) ? &q.df : nullptr, X};
+  a.X.rsv_sel = &q.sel;
+  return a;
+}
+
 // kg_pods_evaluate_reservation: the exact pass's per-node evaluation of one pod (restore, every Filter, nomination,
 // raw Scores) with the restore's state; KG_RSV_EVAL_WORDS int64 per node
 __global__ void evaluate_pod_rsv(DevTable T, const RsvNode* __restrict__ RN, const int32_t* __restrict__ rsv_n,
-                                 const DevPod* __restrict__ pod, const RsvPod* __restrict__ rpod,
-                                 const DsPod* __restrict__ dpod, const NumaPod* __restrict__ npod, int64_t n,
-                                 EvalParams P, RsvParams RP, RsvExt X, int64_t* __restrict__ out) {
+                                 const LonePod* __restrict__ lp, uint32_t on, int64_t n, EvalParams P, RsvParams RP,
+                                 RsvExt X, int64_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   RsvDbg d;
-  const RsvOut o = rsv_eval_node(T, RN, rsv_n, i, *pod, *rpod, P, RP, X, dpod, npod, &d);
+  const LoneArgs a = lone_args(*lp, on, X);
+  const RsvOut o = rsv_eval_node(T, RN, rsv_n, i, lp->pod, lp->rpod, P, RP, a.X, a.dpod, a.npod, &d, a.aux, a.df);
   int64_t* w = out + (size_t)i * KG_RSV_EVAL_WORDS;
   w[0] = o.feas ? 1 : 0;
   w[1] = o.feas ? o.nom : -1;
@@ -3802,6 +3833,30 @@ struct DevBuf {
     p = nullptr;
     n = 0;
   }
+};
+
+// Typed arrays laid out in a buffer of 8-byte words (a DevBuf of int64_t / uint64_t): take<T>(count) reserves the next
+// slot, 8-byte aligned; words() is the total to `ensure`; slot.at(base) is the array once the buffer is there (ensure
+// may reallocate, so a slot holds an offset, not a pointer).
+template <typename T>
+struct Slot {
+  size_t word = 0, count = 0;
+  size_t words() const { return (count * sizeof(T) + 7) / 8; }
+  template <typename W>
+  T* at(W* base) const {
+    static_assert(sizeof(W) == 8, "Slot::at: a buffer of 8-byte words");
+    return reinterpret_cast<T*>(base + word);
+  }
+};
+struct Carver {
+  size_t n = 0;
+  template <typename T>
+  Slot<T> take(size_t count) {
+    const Slot<T> s{n, count};
+    n += s.words();
+    return s;
+  }
+  size_t words() const { return n; }
 };
 
 int64_t bits_for(int64_t v) {
@@ -6451,6 +6506,19 @@ int kg_engine_set_clock(kg_engine* e, int64_t now_unix_nano) {
   return 0;
 }
 
+// NodeResourcesFit on device resources is not accelerated: without DeviceShare in the profile a pod that requests
+// devices is refused.  k >= 0: the pod's index in the queue kg_pods_stage stages; k < 0: a pod outside the queue.
+static int refuse_device_requests(const kg_engine* e, const kg_pod& pod, int64_t k) {
+  if (e->ds_on || !e->cfg.fit_filter) return 0;
+  for (int r = 0; r < KG_DEV_RES_MAX; ++r) {
+    if (pod.device_requests[r] == 0) continue;
+    if (k < 0) return fail(KG_E_UNSUPPORTED, "the pod requests devices; the profile has no DeviceShare");
+    return fail(KG_E_UNSUPPORTED, "pod %lld requests devices; the profile has no DeviceShare (NodeResourcesFit on "
+                "device resources is not accelerated)", (long long)k);
+  }
+  return 0;
+}
+
 int kg_pods_stage(kg_engine* e, const kg_pod* pods, int64_t n) {
   if (!e || (n > 0 && !pods)) return fail(KG_E_INVALID, "null argument");
   for (int64_t k = 0; k < n; ++k) {
@@ -6513,10 +6581,7 @@ int kg_pods_stage(kg_engine* e, const kg_pod* pods, int64_t n) {
     HIP_TRY(hipMemsetAsync(e->out_minors.p, 0, (n + kMaxB) * 4, e->stream));
   } else {
     for (int64_t k = 0; k < n; ++k)
-      for (int r = 0; r < KG_DEV_RES_MAX; ++r)
-        if (pods[k].device_requests[r] != 0 && e->cfg.fit_filter)
-          return fail(KG_E_UNSUPPORTED, "pod %lld requests devices; the profile has no DeviceShare (NodeResourcesFit on "
-                      "device resources is not accelerated)", (long long)k);
+      if (int rc = refuse_device_requests(e, pods[k], k)) return rc;
   }
   if (e->def_on) {  // TaintToleration / NodeAffinity view of the pods
     std::vector<DefPod> hf(std::max<int64_t>(n, 1));
@@ -6771,20 +6836,23 @@ int kg_pods_evaluate(kg_engine* e, const kg_pod* pod, int32_t* out_reject, int64
   if (int rc = decode_pod(e, *pod, d)) return rc;
   const int64_t n = e->n_nodes;
   if (n == 0) return 0;
-  if (int rc = e->scratch64.ensure(2 * n + kPodWords)) return rc;
+  Carver L;
+  const auto s_fit = L.take<int64_t>(n), s_la = L.take<int64_t>(n);
+  const auto s_pod = L.take<DevPod>(1);
+  if (int rc = e->scratch64.ensure(L.words())) return rc;
   if (int rc = e->scratch32.ensure(n)) return rc;
-  DevPod* dp = reinterpret_cast<DevPod*>(e->scratch64.p + 2 * n);  // the kPodWords spare int64s
-  HIP_TRY(hipMemcpyAsync(dp, &d, sizeof(d), hipMemcpyHostToDevice, e->stream));
+  int64_t* b = e->scratch64.p;
+  HIP_TRY(hipMemcpyAsync(s_pod.at(b), &d, sizeof(d), hipMemcpyHostToDevice, e->stream));
   if (int rc = e->paux1.ensure(kAux)) return rc;
   HIP_TRY(hipMemcpyAsync(e->paux1.p, &pod->requests[kAuxFirst], kAux * 8, hipMemcpyHostToDevice, e->stream));
-  evaluate_pod<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(e->T, dp, n, e->P, e->scratch32.p, e->scratch64.p,
-                                                                   e->scratch64.p + n, e->paux1.p);
+  evaluate_pod<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(e->T, s_pod.at(b), n, e->P, e->scratch32.p, s_fit.at(b),
+                                                                   s_la.at(b), e->paux1.p);
   HIP_TRY(hipGetLastError());
   std::vector<int32_t> rej(n);
   std::vector<int64_t> fs(n), ls(n);
   HIP_TRY(hipMemcpyAsync(rej.data(), e->scratch32.p, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(fs.data(), e->scratch64.p, n * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(ls.data(), e->scratch64.p + n, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(fs.data(), s_fit.at(b), n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(ls.data(), s_la.at(b), n * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   // reject bits are only reported for enabled Filter plugins (eval_node checks P.*_filter)
   if (out_reject) std::memcpy(out_reject, rej.data(), n * 4);
@@ -6895,21 +6963,23 @@ int kg_pods_evaluate_numa(kg_engine* e, const kg_pod* pod, int32_t* out_pass, in
   if (int rc = decode_numa_pod(e->cfg, *pod, np)) return rc;
   const int64_t n = e->n_nodes;
   if (n == 0) return 0;
-  if (int rc = e->scratch64.ensure(2 * n + kPodWords + kNumaPodWords)) return rc;
+  Carver L;
+  const auto s_score = L.take<int64_t>(n), s_aff = L.take<int64_t>(n);
+  const auto s_pod = L.take<DevPod>(1);
+  const auto s_np = L.take<NumaPod>(1);
+  if (int rc = e->scratch64.ensure(L.words())) return rc;
   if (int rc = e->scratch32.ensure(n)) return rc;
-  DevPod* dp = reinterpret_cast<DevPod*>(e->scratch64.p + 2 * n);
-  NumaPod* dn = reinterpret_cast<NumaPod*>(e->scratch64.p + 2 * n + kPodWords);
-  HIP_TRY(hipMemcpyAsync(dp, &d, sizeof(d), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(dn, &np, sizeof(np), hipMemcpyHostToDevice, e->stream));
-  evaluate_pod_numa<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(e->T, numa_table(e), dp, dn, n, e->NP,
-                                                                        e->scratch32.p, e->scratch64.p,
-                                                                        e->scratch64.p + n);
+  int64_t* b = e->scratch64.p;
+  HIP_TRY(hipMemcpyAsync(s_pod.at(b), &d, sizeof(d), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(s_np.at(b), &np, sizeof(np), hipMemcpyHostToDevice, e->stream));
+  evaluate_pod_numa<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(e->T, numa_table(e), s_pod.at(b), s_np.at(b), n,
+                                                                        e->NP, e->scratch32.p, s_score.at(b), s_aff.at(b));
   HIP_TRY(hipGetLastError());
   std::vector<int32_t> ps(n);
   std::vector<int64_t> sc(n), af(n);
   HIP_TRY(hipMemcpyAsync(ps.data(), e->scratch32.p, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(sc.data(), e->scratch64.p, n * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(af.data(), e->scratch64.p + n, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(sc.data(), s_score.at(b), n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(af.data(), s_aff.at(b), n * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (out_pass) std::memcpy(out_pass, ps.data(), n * 4);
   if (out_score) std::memcpy(out_score, sc.data(), n * 8);
@@ -6927,11 +6997,15 @@ int kg_nodes_device_upsert(kg_engine* e, const kg_node_device* dev, const int32_
     if (idx[k] < 0 || idx[k] >= e->capacity) return fail(KG_E_INVALID, "node index %d outside capacity", idx[k]);
     if (int rc = decode_node_device(dev[k], h[k], hx[k])) return rc;
   }
-  DevBuf<uint8_t> b;
-  if (int rc = b.ensure(n * (sizeof(DsNode) + sizeof(DsXNode) + 4))) return rc;
-  DsNode* dd = reinterpret_cast<DsNode*>(b.p);
-  DsXNode* dx = reinterpret_cast<DsXNode*>(b.p + n * sizeof(DsNode));
-  int32_t* di = reinterpret_cast<int32_t*>(b.p + n * (sizeof(DsNode) + sizeof(DsXNode)));
+  Carver L;
+  const auto s_d = L.take<DsNode>(n);
+  const auto s_x = L.take<DsXNode>(n);
+  const auto s_i = L.take<int32_t>(n);
+  DevBuf<uint64_t> b;
+  if (int rc = b.ensure(L.words())) return rc;
+  DsNode* dd = s_d.at(b.p);
+  DsXNode* dx = s_x.at(b.p);
+  int32_t* di = s_i.at(b.p);
   HIP_TRY(hipMemcpyAsync(dd, h.data(), n * sizeof(DsNode), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(dx, hx.data(), n * sizeof(DsXNode), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(di, idx, n * 4, hipMemcpyHostToDevice, e->stream));
@@ -7014,17 +7088,20 @@ int kg_pods_evaluate_device(kg_engine* e, const kg_pod* pod, int32_t* out_pass, 
   if (int rc = decode_ds_pod(*pod, dp)) return rc;
   const int64_t n = e->n_nodes;
   if (n == 0) return 0;
-  if (int rc = e->scratch64.ensure(n + kDsPodWords)) return rc;
+  Carver L;
+  const auto s_score = L.take<int64_t>(n);
+  const auto s_dp = L.take<DsPod>(1);
+  if (int rc = e->scratch64.ensure(L.words())) return rc;
   if (int rc = e->scratch32.ensure(n)) return rc;
-  DsPod* d = reinterpret_cast<DsPod*>(e->scratch64.p + n);
-  HIP_TRY(hipMemcpyAsync(d, &dp, sizeof(dp), hipMemcpyHostToDevice, e->stream));
-  evaluate_pod_ds<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(DsTable{e->ds_d.p}, d, n, e->DP, e->scratch32.p,
-                                                                      e->scratch64.p, e->dsx_d.p);
+  int64_t* b = e->scratch64.p;
+  HIP_TRY(hipMemcpyAsync(s_dp.at(b), &dp, sizeof(dp), hipMemcpyHostToDevice, e->stream));
+  evaluate_pod_ds<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(DsTable{e->ds_d.p}, s_dp.at(b), n, e->DP,
+                                                                      e->scratch32.p, s_score.at(b), e->dsx_d.p);
   HIP_TRY(hipGetLastError());
   std::vector<int32_t> ps(n);
   std::vector<int64_t> sc(n);
   HIP_TRY(hipMemcpyAsync(ps.data(), e->scratch32.p, n * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(sc.data(), e->scratch64.p, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(sc.data(), s_score.at(b), n * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (out_pass) std::memcpy(out_pass, ps.data(), n * 4);
   if (out_score) std::memcpy(out_score, sc.data(), n * 8);
@@ -7341,10 +7418,13 @@ int kg_nodes_predicates_upsert(kg_engine* e, const kg_node_predicates* p, const 
     e->np_img_cnt[i] = (int16_t)p[k].image_count;
   }
   e->np_dirty = true;
-  DevBuf<uint8_t> b;
-  if (int rc = b.ensure(n * (sizeof(NodePred) + 4))) return rc;
-  NodePred* dp = reinterpret_cast<NodePred*>(b.p);
-  int32_t* di = reinterpret_cast<int32_t*>(b.p + n * sizeof(NodePred));
+  Carver L;
+  const auto s_p = L.take<NodePred>(n);
+  const auto s_i = L.take<int32_t>(n);
+  DevBuf<uint64_t> b;
+  if (int rc = b.ensure(L.words())) return rc;
+  NodePred* dp = s_p.at(b.p);
+  int32_t* di = s_i.at(b.p);
   HIP_TRY(hipMemcpyAsync(dp, h.data(), n * sizeof(NodePred), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(di, idx, n * 4, hipMemcpyHostToDevice, e->stream));
   scatter_rows<NodePred><<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(e->npred.p, dp, di, n);
@@ -7403,14 +7483,17 @@ int kg_nodes_reservation_upsert(kg_engine* e, const kg_node_reservations* r, con
   std::vector<uint64_t> hp((size_t)n * kRsvSlots);
   for (int64_t k = 0; k < n; ++k)
     for (int s = 0; s < kRsvSlots; ++s) hp[(size_t)k * kRsvSlots + s] = s < r[k].n ? r[k].predicates[s] : 0;
-  DevBuf<uint8_t> b;
-  const size_t pb = (size_t)n * kRsvSlots * 8;
-  if (int rc = b.ensure(pb + n * (sizeof(RsvNode) + 8))) return rc;
-  uint64_t* dp = reinterpret_cast<uint64_t*>(b.p);
-  RsvNode* dd = reinterpret_cast<RsvNode*>(b.p + pb);
-  int32_t* dn = reinterpret_cast<int32_t*>(b.p + pb + n * sizeof(RsvNode));
-  int32_t* di = dn + n;
-  HIP_TRY(hipMemcpyAsync(dp, hp.data(), pb, hipMemcpyHostToDevice, e->stream));
+  Carver L;
+  const auto s_p = L.take<uint64_t>(hp.size());
+  const auto s_d = L.take<RsvNode>(n);
+  const auto s_n = L.take<int32_t>(n), s_i = L.take<int32_t>(n);
+  DevBuf<uint64_t> b;
+  if (int rc = b.ensure(L.words())) return rc;
+  uint64_t* dp = s_p.at(b.p);
+  RsvNode* dd = s_d.at(b.p);
+  int32_t* dn = s_n.at(b.p);
+  int32_t* di = s_i.at(b.p);
+  HIP_TRY(hipMemcpyAsync(dp, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(dd, h.data(), n * sizeof(RsvNode), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(dn, hn.data(), n * 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(di, idx, n * 4, hipMemcpyHostToDevice, e->stream));
@@ -7515,6 +7598,58 @@ int kg_nodes_read_pod_groups(kg_engine* e, int32_t* match_count, int32_t* anti_c
   return 0;
 }
 
+// What decode_lone_pod does for an entry point beyond the records every one of them gets (DevPod, the aux requests,
+// the Reservation view checked against the slots' predicate table, the profile's DsPod and NumaPod).  The entry points
+// grew apart in these; their return codes, messages and the order in which two faults of one pod are reported are ABI.
+enum : uint32_t {
+  LP_DEF = 1u,             // the DefPod of a default-plugin profile, and the pod against the node rows' tables
+  LP_REFUSE_DEVICES = 2u,  // refuse device requests in a profile without DeviceShare
+  LP_REFUSE_X_RGPU = 4u,   // refuse RDMA / FPGA requests while reservations hold GPUs
+  LP_REFUSE_RESERVE = 8u,  // refuse a reserve pod / reservation operating mode (reported before a NUMA / device fault)
+  LP_NUMA_FIRST = 16u,     // a NodeNUMAResource fault is reported before a DeviceShare fault (else after)
+};
+// kg_pods_evaluate_reservation: its kernel reads neither the aux requests nor the DefPod (no LONE_AUX / LONE_DEF), and
+// it has never refused a pod the per-node body evaluates differently from the Go path
+constexpr uint32_t kLoneOptsRsvEval = 0;
+// kg_debug_topn, kg_pods_diagnose: the whole per-node body, with the refusals of the cases that body does not cover
+constexpr uint32_t kLoneOptsDebug = LP_DEF | LP_REFUSE_DEVICES | LP_REFUSE_X_RGPU;
+// the preemption dry run (preempt_prepare, which refuses DeviceShare with GPU-holding reservations for every pod)
+constexpr uint32_t kLoneOptsPreempt = LP_DEF | LP_REFUSE_DEVICES | LP_REFUSE_RESERVE | LP_NUMA_FIRST;
+
+// One pod evaluated outside the staged queue: every record of LonePod decoded and checked as kg_pods_stage does.
+// `k` is the pod's index in the caller's batch (the decoders' messages name it).
+static int decode_lone_pod(kg_engine* e, const kg_pod& pod, int64_t k, uint32_t opts, LonePod& o) {
+  std::memset(&o, 0, sizeof(o));
+  o.dpod.skip = 1;
+  if (int rc = decode_pod(e, pod, o.pod)) return rc;
+  for (int q = 0; q < kAux; ++q) o.aux[q] = pod.requests[kAuxFirst + q];
+  if (int rc = decode_rsv_pod(pod, o.rpod, o.sel, k)) return rc;
+  if (int rc = check_rsv_predicates(e, rsv_pred_top(o.rpod, o.sel))) return rc;
+  if (o.rpod.flags & RP_SEL) o.rpod.aux = 0;  // the record's own selector
+  if ((opts & LP_REFUSE_RESERVE) && (o.rpod.flags & (RP_RESERVE | RP_OPERATING)))
+    return fail(KG_E_UNSUPPORTED, "preemption dry run for a reserve pod / reservation operating mode keeps the Go path");
+  if ((opts & LP_NUMA_FIRST) && e->numa_on)
+    if (int rc = decode_numa_pod(e->cfg, pod, o.npod)) return rc;
+  if (e->ds_on) {
+    if (int rc = decode_ds_pod(pod, o.dpod)) return rc;
+    if ((opts & LP_REFUSE_X_RGPU) && (o.dpod.xq[0] | o.dpod.xq[1]) != 0 && e->rsv_on && e->rgpu_nodes > 0)
+      return fail(KG_E_UNSUPPORTED, "RDMA / FPGA requests with reservations that hold GPUs keep the Go path");
+  } else if (opts & LP_REFUSE_DEVICES) {
+    if (int rc = refuse_device_requests(e, pod, -1)) return rc;
+  }
+  if (!(opts & LP_NUMA_FIRST) && e->numa_on)
+    if (int rc = decode_numa_pod(e->cfg, pod, o.npod)) return rc;
+  if ((opts & LP_DEF) && e->def_on) {
+    if (int rc = decode_def_pod(pod, o.df, k)) return rc;
+    if (int rc = check_pod_tables(e, pod)) return rc;
+  }
+  return 0;
+}
+// the profile's part of the mask the kernels hand to lone_args
+static uint32_t lone_on(const kg_engine* e) {
+  return (e->ds_on ? LONE_DS : 0u) | (e->numa_on ? LONE_NUMA : 0u) | (e->def_on ? LONE_DEF : 0u);
+}
+
 int kg_pods_evaluate_reservation(kg_engine* e, const kg_pod* pod, int64_t* out) {
   if (!e || !pod || !out) return fail(KG_E_INVALID, "null argument");
   if (!e->exact_on) return fail(KG_E_INVALID, "the profile does not run the exact pass (Reservation or NUMA + DeviceShare)");
@@ -7522,85 +7657,24 @@ int kg_pods_evaluate_reservation(kg_engine* e, const kg_pod* pod, int64_t* out) 
     return fail(KG_E_UNSUPPORTED, "kg_pods_evaluate_reservation: PodTopologySpread / InterPodAffinity need the pass's "
                 "cluster-wide reductions (use kg_pods_schedule)");
   if (int rc = sync_static(e)) return rc;
-  DevPod d;
-  if (int rc = decode_pod(e, *pod, d)) return rc;
-  RsvPod rp;
-  RsvSel rs;
-  if (int rc = decode_rsv_pod(*pod, rp, rs, 0)) return rc;
-  if (int rc = check_rsv_predicates(e, rsv_pred_top(rp, rs))) return rc;
-  if (rp.flags & RP_SEL) rp.aux = 0;  // the scratch copy below
-  DsPod dsp{};
-  dsp.skip = 1;
-  if (e->ds_on)
-    if (int rc = decode_ds_pod(*pod, dsp)) return rc;
-  NumaPod np{};
-  if (e->numa_on)
-    if (int rc = decode_numa_pod(e->cfg, *pod, np)) return rc;
+  LonePod lp;  // lives until the stream is synchronised
+  if (int rc = decode_lone_pod(e, *pod, 0, kLoneOptsRsvEval, lp)) return rc;
   const int64_t n = e->n_nodes;
   if (n == 0) return 0;
-  const int64_t words = (int64_t)KG_RSV_EVAL_WORDS * n;
-  const int64_t pw = kPodWords + (int64_t)(sizeof(RsvPod) / 8) + kDsPodWords + kNumaPodWords;
-  if (int rc = e->scratch64.ensure(words + pw + sizeof(RsvSel) / 8)) return rc;
-  RsvSel* gs = reinterpret_cast<RsvSel*>(e->scratch64.p + words + pw);
-  DevPod* gp = reinterpret_cast<DevPod*>(e->scratch64.p + words);
-  RsvPod* gr = reinterpret_cast<RsvPod*>(e->scratch64.p + words + kPodWords);
-  DsPod* gd = reinterpret_cast<DsPod*>(e->scratch64.p + words + kPodWords + sizeof(RsvPod) / 8);
-  NumaPod* gn = reinterpret_cast<NumaPod*>(e->scratch64.p + words + kPodWords + sizeof(RsvPod) / 8 + kDsPodWords);
-  HIP_TRY(hipMemcpyAsync(gp, &d, sizeof(d), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(gr, &rp, sizeof(rp), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(gd, &dsp, sizeof(dsp), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(gn, &np, sizeof(np), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(gs, &rs, sizeof(rs), hipMemcpyHostToDevice, e->stream));
+  Carver L;
+  const auto s_out = L.take<int64_t>((size_t)KG_RSV_EVAL_WORDS * n);
+  const auto s_pod = L.take<LonePod>(1);
+  if (int rc = e->scratch64.ensure(L.words())) return rc;
+  int64_t* b = e->scratch64.p;
+  HIP_TRY(hipMemcpyAsync(s_pod.at(b), &lp, sizeof(lp), hipMemcpyHostToDevice, e->stream));
   RsvExt X = rsv_ext(e);
-  X.rsv_sel = gs;
   X.aff = nullptr;  // no pass affinity store: this is not a scheduling pass
-  evaluate_pod_rsv<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, gp, gr,
-                                                                       e->ds_on ? gd : nullptr,
-                                                                       e->numa_on ? gn : nullptr, n, e->P, e->RP, X,
-                                                                       e->scratch64.p);
+  evaluate_pod_rsv<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, s_pod.at(b),
+                                                                       lone_on(e) & (LONE_DS | LONE_NUMA), n, e->P, e->RP,
+                                                                       X, s_out.at(b));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, e->scratch64.p, words * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out, s_out.at(b), s_out.words() * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  return 0;
-}
-
-// One pod evaluated outside the staged queue (kg_debug_topn, kg_pods_diagnose): every per-plugin record the per-node
-// body reads, decoded and checked as kg_pods_stage does, with the refusals of the cases that body does not cover.
-// `k` is the pod's index in the caller's batch (the decoders' messages name it).
-struct LonePod {
-  DevPod d;
-  int64_t rq[kAux];
-  RsvPod rp;
-  RsvSel rs;
-  DsPod dsp;
-  NumaPod np;
-  DefPod df;
-};
-static int decode_lone_pod(kg_engine* e, const kg_pod& pod, int64_t k, LonePod& o) {
-  if (int rc = decode_pod(e, pod, o.d)) return rc;
-  for (int q = 0; q < kAux; ++q) o.rq[q] = pod.requests[kAuxFirst + q];
-  if (int rc = decode_rsv_pod(pod, o.rp, o.rs, k)) return rc;
-  if (int rc = check_rsv_predicates(e, rsv_pred_top(o.rp, o.rs))) return rc;
-  if (o.rp.flags & RP_SEL) o.rp.aux = 0;  // the caller's scratch copy of the selector
-  o.dsp = DsPod{};
-  o.dsp.skip = 1;
-  if (e->ds_on) {
-    if (int rc = decode_ds_pod(pod, o.dsp)) return rc;
-    if ((o.dsp.xq[0] | o.dsp.xq[1]) != 0 && e->rsv_on && e->rgpu_nodes > 0)
-      return fail(KG_E_UNSUPPORTED, "RDMA / FPGA requests with reservations that hold GPUs keep the Go path");
-  } else {
-    for (int r = 0; r < KG_DEV_RES_MAX; ++r)
-      if (pod.device_requests[r] != 0 && e->cfg.fit_filter)
-        return fail(KG_E_UNSUPPORTED, "the pod requests devices; the profile has no DeviceShare");
-  }
-  o.np = NumaPod{};
-  if (e->numa_on)
-    if (int rc = decode_numa_pod(e->cfg, pod, o.np)) return rc;
-  o.df = DefPod{};
-  if (e->def_on) {
-    if (int rc = decode_def_pod(pod, o.df, k)) return rc;
-    if (int rc = check_pod_tables(e, pod)) return rc;
-  }
   return 0;
 }
 
@@ -7620,80 +7694,52 @@ int kg_debug_topn(kg_engine* e, const kg_pod* pod, int32_t topn, kg_topn_row* ou
     return fail(KG_E_UNSUPPORTED, "kg_debug_topn: the engine shards nodes over %d ranks (a rank holds a part of the "
                 "table; use a one-rank or replica engine)", e->n_ranks);
   if (int rc = sync_static(e)) return rc;
-  LonePod lp;
-  if (int rc = decode_lone_pod(e, *pod, 0, lp)) return rc;
-  const DevPod& d = lp.d;
-  const int64_t (&rq)[kAux] = lp.rq;
-  const RsvPod& rp = lp.rp;
-  const RsvSel& rs = lp.rs;
-  const DsPod& dsp = lp.dsp;
-  const NumaPod& np = lp.np;
-  const DefPod& df = lp.df;
+  LonePod lp;  // lives until the stream is synchronised
+  if (int rc = decode_lone_pod(e, *pod, 0, kLoneOptsDebug, lp)) return rc;
   const int64_t n = e->n_nodes;
   *out_n_rows = 0;
   *out_feasible = 0;
   if (n == 0) return 0;
   const int64_t nb = (n + kRsvThreads - 1) / kRsvThreads;
-  constexpr int64_t kRowWords = (int64_t)(sizeof(kg_topn_row) / 8), kHdrWords = (int64_t)(sizeof(TopnHdr) / 8);
-  static_assert(sizeof(kg_topn_row) % 8 == 0 && sizeof(RsvPod) % 8 == 0 && sizeof(RsvSel) % 8 == 0, "topn scratch layout");
-  // word offsets into the scratch
-  const int64_t o_val = 0, o_val2 = o_val + n, o_part = o_val2 + (n + 1) / 2, o_cand = o_part + 6 * nb,
-                o_win = o_cand + nb * topn, o_pod = o_win + KG_TOPN_MAX, o_rpod = o_pod + kPodWords,
-                o_dpod = o_rpod + (int64_t)(sizeof(RsvPod) / 8), o_npod = o_dpod + kDsPodWords,
-                o_sel = o_npod + kNumaPodWords, o_aux = o_sel + (int64_t)(sizeof(RsvSel) / 8), o_df = o_aux + kAux,
-                o_out = o_df + (int64_t)((sizeof(DefPod) + 7) / 8), words = o_out + kHdrWords + kRowWords * KG_TOPN_MAX;
-  if (int rc = e->topn_buf.ensure((size_t)words)) return rc;
+  static_assert(sizeof(kg_topn_row) % 8 == 0 && sizeof(TopnHdr) % 8 == 0, "topn output: header and rows in one copy");
+  Carver L;
+  const auto s_val = L.take<uint64_t>(n);
+  const auto s_val2 = L.take<uint32_t>(n);
+  const auto s_part = L.take<uint64_t>(6 * nb);  // one array: part[k * nb + b]
+  const auto s_cand = L.take<uint64_t>(nb * topn), s_win = L.take<uint64_t>(KG_TOPN_MAX);
+  const auto s_pod = L.take<LonePod>(1);
+  const auto s_hdr = L.take<TopnHdr>(1);  // the header, then the rows: one copy back
+  const auto s_rows = L.take<kg_topn_row>(KG_TOPN_MAX);
+  if (int rc = e->topn_buf.ensure(L.words())) return rc;
   uint64_t* b = e->topn_buf.p;
-  DevPod* gp = reinterpret_cast<DevPod*>(b + o_pod);
-  RsvPod* gr = reinterpret_cast<RsvPod*>(b + o_rpod);
-  DsPod* gd = reinterpret_cast<DsPod*>(b + o_dpod);
-  NumaPod* gn = reinterpret_cast<NumaPod*>(b + o_npod);
-  RsvSel* gs = reinterpret_cast<RsvSel*>(b + o_sel);
-  int64_t* ga = reinterpret_cast<int64_t*>(b + o_aux);
-  DefPod* gf = reinterpret_cast<DefPod*>(b + o_df);
-  TopnHdr* gh = reinterpret_cast<TopnHdr*>(b + o_out);
-  kg_topn_row* grows = reinterpret_cast<kg_topn_row*>(b + o_out + kHdrWords);
-  // the pod's records are adjacent in the scratch: packed on the host, one copy (hp lives until the stream is synchronised)
-  uint64_t hp[(sizeof(DevPod) + sizeof(RsvPod) + sizeof(DsPod) + sizeof(NumaPod) + sizeof(RsvSel) + sizeof(rq) +
-               sizeof(DefPod) + 7 * 8) / 8] = {};
-  static_assert(sizeof(DevPod) == kPodWords * 8 && sizeof(DsPod) <= kDsPodWords * 8 && sizeof(NumaPod) <= kNumaPodWords * 8,
-                "topn pod records");
-  if ((size_t)(o_out - o_pod) * 8 > sizeof(hp)) return fail(KG_E_INVALID, "kg_debug_topn: pod record layout");
-  std::memcpy(hp + (o_pod - o_pod), &d, sizeof(d));
-  std::memcpy(hp + (o_rpod - o_pod), &rp, sizeof(rp));
-  std::memcpy(hp + (o_dpod - o_pod), &dsp, sizeof(dsp));
-  std::memcpy(hp + (o_npod - o_pod), &np, sizeof(np));
-  std::memcpy(hp + (o_sel - o_pod), &rs, sizeof(rs));
-  std::memcpy(hp + (o_aux - o_pod), rq, sizeof(rq));
-  std::memcpy(hp + (o_df - o_pod), &df, sizeof(df));
-  HIP_TRY(hipMemcpyAsync(gp, hp, (size_t)(o_out - o_pod) * 8, hipMemcpyHostToDevice, e->stream));
+  const LonePod* gp = s_pod.at(b);
+  HIP_TRY(hipMemcpyAsync(s_pod.at(b), &lp, sizeof(lp), hipMemcpyHostToDevice, e->stream));
   RsvExt X = rsv_ext(e);
-  X.rsv_sel = gs;
   X.aff = nullptr;  // no pass affinity store: this is not a scheduling pass
-  X.val2 = e->def_score ? reinterpret_cast<uint32_t*>(b + o_val2) : nullptr;
+  X.val2 = e->def_score ? s_val2.at(b) : nullptr;
   X.gpods = nullptr;
-  const TopnPod tp{gp, gr, e->ds_on ? gd : nullptr, e->numa_on ? gn : nullptr, (d.flags & P_AUX) ? ga : nullptr,
-                   e->def_on ? gf : nullptr};
+  const uint32_t on = lone_on(e) | LONE_AUX;
   const kg_config& c = e->cfg;
   const uint32_t en = (c.fit_score ? 1u << KG_PL_FIT : 0u) | (c.la_score ? 1u << KG_PL_LOADAWARE : 0u) |
                       (c.numa_score ? 1u << KG_PL_NUMA : 0u) | (c.ds_score ? 1u << KG_PL_DEVICESHARE : 0u) |
                       (c.reservation_score ? 1u << KG_PL_RESERVATION : 0u) | (c.taint_score ? 1u << KG_PL_TAINT : 0u) |
                       (c.affinity_score ? 1u << KG_PL_NODE_AFFINITY : 0u) | (c.balanced_score ? 1u << KG_PL_BALANCED : 0u) |
                       (c.image_score ? 1u << KG_PL_IMAGE_LOCALITY : 0u);
-  topn_eval<<<(unsigned)nb, kRsvThreads, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, tp, n, e->P, e->RP, X, b + o_val,
-                                                         b + o_part);
-  topn_select<<<(unsigned)nb, kRsvThreads, 0, e->stream>>>(b + o_val, n, (int)topn, e->RP, X, b + o_part, b + o_cand);
-  topn_final<<<1, kTopnFinalThreads, 0, e->stream>>>(b + o_cand, nb * topn, (int)nb, (int)topn, b + o_part, b + o_win, gh);
-  topn_gather<<<1, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, tp, (int)nb, e->P, e->RP, X, b + o_part,
-                                          b + o_win, gh, en, grows);
+  topn_eval<<<(unsigned)nb, kRsvThreads, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, gp, on, n, e->P, e->RP, X,
+                                                         s_val.at(b), s_part.at(b));
+  topn_select<<<(unsigned)nb, kRsvThreads, 0, e->stream>>>(s_val.at(b), n, (int)topn, e->RP, X, s_part.at(b), s_cand.at(b));
+  topn_final<<<1, kTopnFinalThreads, 0, e->stream>>>(s_cand.at(b), nb * topn, (int)nb, (int)topn, s_part.at(b),
+                                                     s_win.at(b), s_hdr.at(b));
+  topn_gather<<<1, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, gp, on, (int)nb, e->P, e->RP, X, s_part.at(b),
+                                          s_win.at(b), s_hdr.at(b), en, s_rows.at(b));
   HIP_TRY(hipGetLastError());
-  std::vector<uint64_t> host((size_t)(kHdrWords + kRowWords * topn));
-  HIP_TRY(hipMemcpyAsync(host.data(), b + o_out, host.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  std::vector<uint64_t> host(s_hdr.words() + sizeof(kg_topn_row) / 8 * (size_t)topn);
+  HIP_TRY(hipMemcpyAsync(host.data(), s_hdr.at(b), host.size() * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   TopnHdr h;
   std::memcpy(&h, host.data(), sizeof(h));
   if (h.n_rows < 0 || h.n_rows > topn) return fail(KG_E_DEVICE, "kg_debug_topn: %lld rows", (long long)h.n_rows);
-  std::memcpy(out_rows, host.data() + kHdrWords, (size_t)h.n_rows * sizeof(kg_topn_row));
+  std::memcpy(out_rows, host.data() + s_hdr.words(), (size_t)h.n_rows * sizeof(kg_topn_row));
   *out_n_rows = h.n_rows;
   *out_feasible = h.feasible;
   return 0;
@@ -7718,41 +7764,36 @@ int kg_pods_diagnose(kg_engine* e, const kg_pod* pods, int64_t n_pods, kg_fit_di
                 "table; use a one-rank or replica engine)", e->n_ranks);
   if (n_pods == 0) return 0;
   if (int rc = sync_static(e)) return rc;
-  std::vector<DiagPod> hp((size_t)n_pods);  // lives until the stream is synchronised
+  std::vector<LonePod> hp((size_t)n_pods);  // lives until the stream is synchronised
   for (int64_t k = 0; k < n_pods; ++k) {
-    LonePod lp;
-    if (int rc = decode_lone_pod(e, pods[k], k, lp)) {
+    if (int rc = decode_lone_pod(e, pods[k], k, kLoneOptsDebug, hp[(size_t)k])) {
       const std::string why = g_err;
       return fail(rc, "kg_pods_diagnose: pod %lld of the batch: %s", (long long)k, why.c_str());
     }
-    DiagPod& q = hp[(size_t)k];
-    std::memset(&q, 0, sizeof(q));
-    q.pod = lp.d, q.rpod = lp.rp, q.sel = lp.rs, q.dpod = lp.dsp, q.npod = lp.np, q.df = lp.df;
-    std::memcpy(q.aux, lp.rq, sizeof(lp.rq));
   }
   const int64_t n = e->n_nodes;
   std::memset(out_diag, 0, (size_t)n_pods * sizeof(kg_fit_diag));
   if (n == 0) return 0;
   const int64_t nb = (n + kRsvThreads - 1) / kRsvThreads;
-  constexpr int64_t kPodW = (int64_t)(sizeof(DiagPod) / 8), kOutW = (int64_t)(sizeof(kg_fit_diag) / 8);
-  static_assert(sizeof(kg_fit_diag) % 8 == 0, "diag scratch layout");
   const int64_t chunk = std::min<int64_t>(n_pods, kDiagChunk);
-  // word offsets into the scratch: every pod's records and result, one chunk's partial rows and status words
-  const int64_t o_pods = 0, o_out = o_pods + n_pods * kPodW, o_part = o_out + n_pods * kOutW,
-                o_st = o_part + (chunk * nb * kDiagRow + 1) / 2,
-                words = o_st + (out_node_status ? (chunk * n + 1) / 2 : 0);
-  if (int rc = e->diag_buf.ensure((size_t)words)) return rc;
+  // every pod's records and result, one chunk's partial rows and status words
+  Carver L;
+  const auto s_pods = L.take<LonePod>(n_pods);
+  const auto s_out = L.take<kg_fit_diag>(n_pods);
+  const auto s_part = L.take<uint32_t>(chunk * nb * kDiagRow);
+  const auto s_st = L.take<int32_t>(out_node_status ? chunk * n : 0);
+  if (int rc = e->diag_buf.ensure(L.words())) return rc;
   uint64_t* b = e->diag_buf.p;
-  DiagPod* gp = reinterpret_cast<DiagPod*>(b + o_pods);
-  kg_fit_diag* go = reinterpret_cast<kg_fit_diag*>(b + o_out);
-  uint32_t* gpart = reinterpret_cast<uint32_t*>(b + o_part);
-  int32_t* gst = out_node_status ? reinterpret_cast<int32_t*>(b + o_st) : nullptr;
-  HIP_TRY(hipMemcpyAsync(gp, hp.data(), (size_t)n_pods * sizeof(DiagPod), hipMemcpyHostToDevice, e->stream));
+  const LonePod* gp = s_pods.at(b);
+  kg_fit_diag* go = s_out.at(b);
+  uint32_t* gpart = s_part.at(b);
+  int32_t* gst = out_node_status ? s_st.at(b) : nullptr;
+  HIP_TRY(hipMemcpyAsync(s_pods.at(b), hp.data(), (size_t)n_pods * sizeof(LonePod), hipMemcpyHostToDevice, e->stream));
   RsvExt X = rsv_ext(e);
   X.aff = nullptr;  // no pass affinity store: this is not a scheduling pass
   X.val2 = nullptr;
   X.gpods = nullptr;
-  const uint32_t on = (e->ds_on ? DIAG_DS : 0u) | (e->numa_on ? DIAG_NUMA : 0u) | (e->def_on ? DIAG_DEF : 0u);
+  const uint32_t on = lone_on(e) | LONE_AUX;
   for (int64_t c0 = 0; c0 < n_pods; c0 += chunk) {
     const int64_t cn = std::min<int64_t>(chunk, n_pods - c0);
     // pod groups: as many as fill the device with node blocks alone when the table is large, one pod per block row
@@ -7771,13 +7812,14 @@ int kg_pods_diagnose(kg_engine* e, const kg_pod* pods, int64_t n_pods, kg_fit_di
   return 0;
 }
 
-// the pod and its victims of one dry-run call, decoded and checked (the shared front half of the two entry points).
+// the pod and its victims of one dry-run call, decoded and checked (the shared front half of the entry points): the
+// pod through decode_lone_pod, from which PreExt — the kernels' by-value argument — is filled.
 // (r6) NodeNUMAResource, DeviceShare and TaintToleration / NodeAffinity run in the dry run too (PreExt); refused:
 // PodTopologySpread / InterPodAffinity (their PreFilterExtensions move cluster-wide counters) and DeviceShare with
 // reservations that hold GPUs (preemptibleInRRs of devices).
 static int preempt_prepare(kg_engine* e, const kg_pod* pod, const kg_pod* victims, const int32_t* victim_slot,
-                           const int32_t* victim_minors, int64_t n_victims, DevPod& d, RsvPod& rp, RsvSel& rs,
-                           int64_t (&rq)[kAux], std::vector<Victim>& hv, PreExt& X) {
+                           const int32_t* victim_minors, int64_t n_victims, LonePod& lp, std::vector<Victim>& hv,
+                           PreExt& X) {
   if (e->grp_on)
     return fail(KG_E_UNSUPPORTED, "preemption dry run: PodTopologySpread / InterPodAffinity keep the Go path (their "
                 "AddPod / RemovePod move cluster-wide counters)");
@@ -7785,32 +7827,12 @@ static int preempt_prepare(kg_engine* e, const kg_pod* pod, const kg_pod* victim
     return fail(KG_E_UNSUPPORTED, "preemption dry run: DeviceShare with reservations that hold GPUs keeps the Go path "
                 "(preemptibleInRRs of devices)");
   if (int rc = sync_static(e)) return rc;
-  if (int rc = decode_pod(e, *pod, d)) return rc;
-  for (int q = 0; q < kAux; ++q) rq[q] = pod->requests[kAuxFirst + q];
-  if (int rc = decode_rsv_pod(*pod, rp, rs, 0)) return rc;
-  if (int rc = check_rsv_predicates(e, rsv_pred_top(rp, rs))) return rc;
-  if (rp.flags & RP_SEL) rp.aux = 0;
-  if (rp.flags & (RP_RESERVE | RP_OPERATING))
-    return fail(KG_E_UNSUPPORTED, "preemption dry run for a reserve pod / reservation operating mode keeps the Go path");
+  if (int rc = decode_lone_pod(e, *pod, 0, kLoneOptsPreempt, lp)) return rc;
   X = PreExt{};
-  X.dp.skip = 1;
-  if (e->numa_on) {
-    if (int rc = decode_numa_pod(e->cfg, *pod, X.np)) return rc;
-    X.ns = e->numa_s.p, X.nm = e->numa_m.p, X.NP = e->NP;
-  }
-  if (e->ds_on) {
-    if (int rc = decode_ds_pod(*pod, X.dp)) return rc;
-    X.ds = e->ds_d.p, X.dsx = e->dsx_d.p, X.DP = e->DP;
-  } else {
-    for (int r = 0; r < KG_DEV_RES_MAX; ++r)
-      if (pod->device_requests[r] != 0 && e->cfg.fit_filter)
-        return fail(KG_E_UNSUPPORTED, "the pod requests devices; the profile has no DeviceShare");
-  }
-  if (e->def_on) {
-    if (int rc = decode_def_pod(*pod, X.df, 0)) return rc;
-    if (int rc = check_pod_tables(e, *pod)) return rc;
-    X.pred = e->npred.p, X.DF = e->DF;
-  }
+  X.np = lp.npod, X.dp = lp.dpod, X.df = lp.df;
+  if (e->numa_on) X.ns = e->numa_s.p, X.nm = e->numa_m.p, X.NP = e->NP;
+  if (e->ds_on) X.ds = e->ds_d.p, X.dsx = e->dsx_d.p, X.DP = e->DP;
+  if (e->def_on) X.pred = e->npred.p, X.DF = e->DF;
   hv.resize((size_t)std::max<int64_t>(n_victims, 1));
   for (int64_t k = 0; k < n_victims; ++k) {
     DevPod v;
@@ -7847,28 +7869,28 @@ int kg_pods_filter_preemption(kg_engine* e, const kg_pod* pod, int32_t node_idx,
   if (!e || !pod || !out_reject || n_victims < 0 || (n_victims > 0 && !victims)) return fail(KG_E_INVALID, "null argument");
   if (node_idx < 0 || node_idx >= e->n_nodes) return fail(KG_E_INVALID, "node index %d outside [0, %lld)", node_idx,
                                                            (long long)e->n_nodes);
-  DevPod d;
-  RsvPod rp;
-  RsvSel rs;
-  int64_t rq[kAux];
+  LonePod lp;  // lives until the stream is synchronised
   std::vector<Victim> hv;
   PreExt X;
-  if (int rc = preempt_prepare(e, pod, victims, victim_slot, victim_minors, n_victims, d, rp, rs, rq, hv, X)) return rc;
-  const size_t vw = (hv.size() * sizeof(Victim) + 7) / 8;
-  if (int rc = e->scratch64.ensure(kPodWords + kAux + vw + 1 + sizeof(RsvSel) / 8)) return rc;
-  DevPod* gp = reinterpret_cast<DevPod*>(e->scratch64.p);
-  int64_t* ga = reinterpret_cast<int64_t*>(e->scratch64.p + kPodWords);
-  Victim* gv = reinterpret_cast<Victim*>(e->scratch64.p + kPodWords + kAux);
-  int32_t* go = reinterpret_cast<int32_t*>(e->scratch64.p + kPodWords + kAux + vw);
-  RsvSel* gs = reinterpret_cast<RsvSel*>(e->scratch64.p + kPodWords + kAux + vw + 1);
-  HIP_TRY(hipMemcpyAsync(gp, &d, sizeof(d), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(ga, rq, sizeof(rq), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(gs, &rs, sizeof(rs), hipMemcpyHostToDevice, e->stream));
-  if (n_victims > 0) HIP_TRY(hipMemcpyAsync(gv, hv.data(), (size_t)n_victims * sizeof(Victim), hipMemcpyHostToDevice, e->stream));
-  filter_pod_preempt<<<1, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, e->rsv_pd.p, gs, node_idx, gp, ga, rp,
-                                                 e->P, e->RP, e->rsv_on ? 1 : 0, gv, n_victims, go, X);
+  if (int rc = preempt_prepare(e, pod, victims, victim_slot, victim_minors, n_victims, lp, hv, X)) return rc;
+  Carver L;  // the kernel's loose arguments, as the dry run lays them out (DryRunLayout)
+  const auto s_pod = L.take<DevPod>(1);
+  const auto s_aux = L.take<int64_t>(kAux);
+  const auto s_vic = L.take<Victim>(hv.size());
+  const auto s_out = L.take<int32_t>(1);
+  const auto s_sel = L.take<RsvSel>(1);
+  if (int rc = e->scratch64.ensure(L.words())) return rc;
+  int64_t* b = e->scratch64.p;
+  HIP_TRY(hipMemcpyAsync(s_pod.at(b), &lp.pod, sizeof(lp.pod), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(s_aux.at(b), lp.aux, sizeof(lp.aux), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(s_sel.at(b), &lp.sel, sizeof(lp.sel), hipMemcpyHostToDevice, e->stream));
+  if (n_victims > 0)
+    HIP_TRY(hipMemcpyAsync(s_vic.at(b), hv.data(), (size_t)n_victims * sizeof(Victim), hipMemcpyHostToDevice, e->stream));
+  filter_pod_preempt<<<1, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, e->rsv_pd.p, s_sel.at(b), node_idx,
+                                                 s_pod.at(b), s_aux.at(b), lp.rpod, e->P, e->RP, e->rsv_on ? 1 : 0,
+                                                 s_vic.at(b), n_victims, s_out.at(b), X);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out_reject, go, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_reject, s_out.at(b), 4, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -7891,60 +7913,49 @@ static int candidates_check(kg_engine* e, int64_t n_candidates, const int32_t* n
   return 0;
 }
 
-// word offsets of one dry-run call's device buffer: pod, pod aux, RsvSel, victims, offsets, nodes, violating flags, then
-// the outputs; `end` = the first word behind them
+// one dry-run call's device arrays: the pod (the kernel's loose arguments, each uploaded from its LonePod member: one
+// LonePod copy in front of the victims measured twice the call time at 100k candidates), its victims and the
+// candidates in, select_victims' three outputs out
 struct DryRunLayout {
-  size_t o_pod, o_aux, o_sel, o_vic, o_off, o_nodes, o_viol, o_rej, o_out, o_nvio, end;
+  Slot<DevPod> pod;
+  Slot<int64_t> aux;
+  Slot<RsvSel> sel;
+  Slot<Victim> vic;
+  Slot<int64_t> off;
+  Slot<int32_t> nodes;
+  Slot<uint8_t> viol;
+  Slot<int32_t> rej;   // per candidate
+  Slot<uint8_t> out;   // per victim
+  Slot<int32_t> nvio;  // per candidate
 };
+static DryRunLayout dry_run_layout(Carver& C, int64_t n_candidates, int64_t nv, size_t n_vic) {
+  const size_t nc = (size_t)n_candidates, nvs = (size_t)std::max<int64_t>(nv, 1);
+  return DryRunLayout{C.take<DevPod>(1),       C.take<int64_t>(kAux), C.take<RsvSel>(1),    C.take<Victim>(n_vic),
+                      C.take<int64_t>(nc + 1), C.take<int32_t>(nc),   C.take<uint8_t>(nvs), C.take<int32_t>(nc),
+                      C.take<uint8_t>(nvs),    C.take<int32_t>(nc)};
+}
 
-// uploads one dry-run call into `buf` (grown to the layout plus `tail` words for the caller) and launches select_victims
-// over it on the engine stream; the outputs stay on the device
-static int dry_run_launch(kg_engine* e, DevBuf<int64_t>& buf, size_t tail, int64_t n_candidates, const int32_t* node_idx,
-                          const int64_t* victim_offsets, int64_t nv, const uint8_t* pdb_violating, const DevPod& d,
-                          const RsvPod& rp, const RsvSel& rs, const int64_t (&rq)[kAux], const std::vector<Victim>& hv,
-                          const PreExt& X, DryRunLayout& L) {
-  auto words = [](size_t bytes) { return (bytes + 7) / 8; };
-  const size_t w_pod = kPodWords, w_aux = kAux, w_sel = words(sizeof(RsvSel)), w_vic = words(hv.size() * sizeof(Victim));
-  const size_t w_off = (size_t)n_candidates + 1, w_nodes = words((size_t)n_candidates * 4),
-               w_viol = words((size_t)std::max<int64_t>(nv, 1)), w_rej = words((size_t)n_candidates * 4),
-               w_out = words((size_t)std::max<int64_t>(nv, 1)), w_nvio = words((size_t)n_candidates * 4);
-  size_t o = 0;
-  L.o_pod = o; o += w_pod;
-  L.o_aux = o; o += w_aux;
-  L.o_sel = o; o += w_sel;
-  L.o_vic = o; o += w_vic;
-  L.o_off = o; o += w_off;
-  L.o_nodes = o; o += w_nodes;
-  L.o_viol = o; o += w_viol;
-  L.o_rej = o; o += w_rej;
-  L.o_out = o; o += w_out;
-  L.o_nvio = o; o += w_nvio;
-  L.end = o;
-  if (int rc = buf.ensure(o + tail)) return rc;
-  int64_t* b = buf.p;
-  HIP_TRY(hipMemcpyAsync(b + L.o_pod, &d, sizeof(d), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + L.o_aux, rq, sizeof(rq), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + L.o_sel, &rs, sizeof(rs), hipMemcpyHostToDevice, e->stream));
-  if (nv > 0) HIP_TRY(hipMemcpyAsync(b + L.o_vic, hv.data(), (size_t)nv * sizeof(Victim), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + L.o_off, victim_offsets, w_off * 8, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + L.o_nodes, node_idx, (size_t)n_candidates * 4, hipMemcpyHostToDevice, e->stream));
+// uploads one dry-run call into its arrays in `b` and launches select_victims over them on the engine stream; the
+// outputs stay on the device
+static int dry_run_launch(kg_engine* e, int64_t* b, const DryRunLayout& L, int64_t n_candidates, const int32_t* node_idx,
+                          const int64_t* victim_offsets, int64_t nv, const uint8_t* pdb_violating, const LonePod& lp,
+                          const std::vector<Victim>& hv, const PreExt& X) {
+  HIP_TRY(hipMemcpyAsync(L.pod.at(b), &lp.pod, sizeof(lp.pod), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(L.aux.at(b), lp.aux, sizeof(lp.aux), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(L.sel.at(b), &lp.sel, sizeof(lp.sel), hipMemcpyHostToDevice, e->stream));
+  if (nv > 0) HIP_TRY(hipMemcpyAsync(L.vic.at(b), hv.data(), (size_t)nv * sizeof(Victim), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(L.off.at(b), victim_offsets, L.off.count * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(L.nodes.at(b), node_idx, (size_t)n_candidates * 4, hipMemcpyHostToDevice, e->stream));
   const uint8_t* gviol = nullptr;
   if (pdb_violating && nv > 0) {
-    HIP_TRY(hipMemcpyAsync(b + L.o_viol, pdb_violating, (size_t)nv, hipMemcpyHostToDevice, e->stream));
-    gviol = reinterpret_cast<const uint8_t*>(b + L.o_viol);
+    HIP_TRY(hipMemcpyAsync(L.viol.at(b), pdb_violating, (size_t)nv, hipMemcpyHostToDevice, e->stream));
+    gviol = L.viol.at(b);
   }
   const unsigned blocks = (unsigned)((n_candidates + kWave - 1) / kWave);
-  select_victims<<<blocks, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, e->rsv_pd.p,
-                                                  reinterpret_cast<const RsvSel*>(b + L.o_sel),
-                                                  reinterpret_cast<const DevPod*>(b + L.o_pod),
-                                                  reinterpret_cast<const int64_t*>(b + L.o_aux), rp, e->P, e->RP,
-                                                  e->rsv_on ? 1 : 0, n_candidates,
-                                                  reinterpret_cast<const int32_t*>(b + L.o_nodes),
-                                                  reinterpret_cast<const int64_t*>(b + L.o_off),
-                                                  reinterpret_cast<const Victim*>(b + L.o_vic), gviol,
-                                                  reinterpret_cast<int32_t*>(b + L.o_rej),
-                                                  reinterpret_cast<uint8_t*>(b + L.o_out),
-                                                  reinterpret_cast<int32_t*>(b + L.o_nvio), X);
+  select_victims<<<blocks, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, e->rsv_pd.p, L.sel.at(b), L.pod.at(b),
+                                                  L.aux.at(b), lp.rpod, e->P, e->RP, e->rsv_on ? 1 : 0, n_candidates,
+                                                  L.nodes.at(b), L.off.at(b), L.vic.at(b), gviol, L.rej.at(b),
+                                                  L.out.at(b), L.nvio.at(b), X);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -7960,21 +7971,18 @@ int kg_pods_select_victims(kg_engine* e, const kg_pod* pod, int64_t n_candidates
   int64_t nv, max_seg;
   if (int rc = candidates_check(e, n_candidates, node_idx, victim_offsets, nv, max_seg)) return rc;
   if (nv > 0 && (!victims || !out_victim)) return fail(KG_E_INVALID, "null argument");
-  DevPod d;
-  RsvPod rp;
-  RsvSel rs;
-  int64_t rq[kAux];
+  LonePod lp;  // lives until the stream is synchronised
   std::vector<Victim> hv;
   PreExt X;
-  if (int rc = preempt_prepare(e, pod, victims, victim_slot, victim_minors, nv, d, rp, rs, rq, hv, X)) return rc;
-  DryRunLayout L;
-  if (int rc = dry_run_launch(e, e->scratch64, 0, n_candidates, node_idx, victim_offsets, nv, pdb_violating, d, rp, rs, rq,
-                              hv, X, L))
-    return rc;
-  const int64_t* b = e->scratch64.p;
-  HIP_TRY(hipMemcpyAsync(out_reject, b + L.o_rej, (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(out_violating, b + L.o_nvio, (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
-  if (nv > 0) HIP_TRY(hipMemcpyAsync(out_victim, b + L.o_out, (size_t)nv, hipMemcpyDeviceToHost, e->stream));
+  if (int rc = preempt_prepare(e, pod, victims, victim_slot, victim_minors, nv, lp, hv, X)) return rc;
+  Carver C;
+  const DryRunLayout L = dry_run_layout(C, n_candidates, nv, hv.size());
+  if (int rc = e->scratch64.ensure(C.words())) return rc;
+  int64_t* b = e->scratch64.p;
+  if (int rc = dry_run_launch(e, b, L, n_candidates, node_idx, victim_offsets, nv, pdb_violating, lp, hv, X)) return rc;
+  HIP_TRY(hipMemcpyAsync(out_reject, L.rej.at(b), (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_violating, L.nvio.at(b), (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
+  if (nv > 0) HIP_TRY(hipMemcpyAsync(out_victim, L.out.at(b), (size_t)nv, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -7989,28 +7997,31 @@ struct PickDev {
   const int32_t* nvio;
   const int32_t* prio;
   const int64_t* start;
-  int64_t* tail;  // pick_tail_words(n_candidates, max_seg) words: keys, partials, the output
 };
-static size_t pick_tail_words(int64_t n_candidates, int64_t max_seg) {
-  return (size_t)n_candidates * (sizeof(PickKey) / 8) + (size_t)kPickBlocks * (sizeof(PickPart) / 8) +
-         sizeof(kg_preempt_pick) / 8 + (size_t)(max_seg + 1) / 2;
+// the pick's own arrays behind a call's inputs: keys, partials, then the output (the header and the victim positions,
+// adjacent: one copy back)
+struct PickTail {
+  Slot<PickKey> key;
+  Slot<PickPart> part;
+  Slot<kg_preempt_pick> hdr;
+  Slot<int32_t> vic;
+};
+static PickTail pick_tail(Carver& C, int64_t n_candidates, int64_t max_seg) {
+  static_assert(sizeof(kg_preempt_pick) % 8 == 0, "pick output: header and victims in one copy");
+  return PickTail{C.take<PickKey>((size_t)n_candidates), C.take<PickPart>(kPickBlocks), C.take<kg_preempt_pick>(1),
+                  C.take<int32_t>((size_t)max_seg)};
 }
-static int pick_run(kg_engine* e, int64_t n_candidates, int64_t max_seg, const PickDev& D, kg_preempt_pick* out_pick,
-                    int32_t* out_victims) {
-  static_assert(sizeof(PickKey) == 32 && sizeof(PickPart) == 40 && sizeof(kg_preempt_pick) == 64, "pick scratch layout");
-  PickKey* gkey = reinterpret_cast<PickKey*>(D.tail);
-  PickPart* gpart = reinterpret_cast<PickPart*>(D.tail + n_candidates * 4);
-  int64_t* gout = D.tail + n_candidates * 4 + kPickBlocks * 5;
-  kg_preempt_pick* ghdr = reinterpret_cast<kg_preempt_pick*>(gout);
-  int32_t* gvic = reinterpret_cast<int32_t*>(gout + 8);
+static int pick_run(kg_engine* e, int64_t n_candidates, int64_t max_seg, const PickDev& D, const PickTail& t, int64_t* b,
+                    kg_preempt_pick* out_pick, int32_t* out_victims) {
   const int64_t nb = (n_candidates + kPickWaves - 1) / kPickWaves;
   const int np = (int)std::min<int64_t>((n_candidates + kPickThreads - 1) / kPickThreads, kPickBlocks);
-  pick_keys<<<(unsigned)nb, kPickThreads, 0, e->stream>>>(n_candidates, D.off, D.rej, D.kept, D.nvio, D.prio, D.start, gkey);
-  pick_reduce<<<(unsigned)np, kPickThreads, 0, e->stream>>>(gkey, n_candidates, gpart);
-  pick_final<<<1, kPickThreads, 0, e->stream>>>(gpart, np, D.nodes, D.off, D.kept, ghdr, gvic, max_seg);
+  pick_keys<<<(unsigned)nb, kPickThreads, 0, e->stream>>>(n_candidates, D.off, D.rej, D.kept, D.nvio, D.prio, D.start,
+                                                          t.key.at(b));
+  pick_reduce<<<(unsigned)np, kPickThreads, 0, e->stream>>>(t.key.at(b), n_candidates, t.part.at(b));
+  pick_final<<<1, kPickThreads, 0, e->stream>>>(t.part.at(b), np, D.nodes, D.off, D.kept, t.hdr.at(b), t.vic.at(b), max_seg);
   HIP_TRY(hipGetLastError());
-  std::vector<int64_t> host(8 + (size_t)(max_seg + 1) / 2);
-  HIP_TRY(hipMemcpyAsync(host.data(), gout, host.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  std::vector<int64_t> host(t.hdr.words() + t.vic.words());
+  HIP_TRY(hipMemcpyAsync(host.data(), t.hdr.at(b), host.size() * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   kg_preempt_pick h;
   std::memcpy(&h, host.data(), sizeof(h));
@@ -8018,7 +8029,7 @@ static int pick_run(kg_engine* e, int64_t n_candidates, int64_t max_seg, const P
     return fail(KG_E_DEVICE, "preemption pick: candidate %lld with %lld victims", (long long)h.candidate,
                 (long long)h.n_victims);
   *out_pick = h;
-  if (h.n_victims > 0) std::memcpy(out_victims, host.data() + 8, (size_t)h.n_victims * 4);
+  if (h.n_victims > 0) std::memcpy(out_victims, host.data() + t.hdr.words(), (size_t)h.n_victims * 4);
   return 0;
 }
 static const kg_preempt_pick kPickNoCandidate = {-1, -1, 0, 0, 0, 0, 0, 0};
@@ -8047,26 +8058,27 @@ int kg_pods_pick_candidate(kg_engine* e, int64_t n_candidates, const int32_t* no
   for (int64_t c = 0; c < n_candidates; ++c)
     if (num_violating[c] < 0)
       return fail(KG_E_INVALID, "candidate %lld: num_violating %d", (long long)c, num_violating[c]);
-  auto words = [](size_t bytes) { return (bytes + 7) / 8; };
   const size_t nc = (size_t)n_candidates, nvs = (size_t)std::max<int64_t>(nv, 1);
-  const size_t o_off = 0, o_nodes = o_off + nc + 1, o_rej = o_nodes + words(nc * 4), o_nvio = o_rej + words(nc * 4),
-               o_kept = o_nvio + words(nc * 4), o_prio = o_kept + words(nvs), o_start = o_prio + words(nvs * 4),
-               o_tail = o_start + nvs;
-  if (int rc = e->pick_buf.ensure(o_tail + pick_tail_words(n_candidates, max_seg))) return rc;
+  Carver C;
+  const auto s_off = C.take<int64_t>(nc + 1);
+  const auto s_nodes = C.take<int32_t>(nc), s_rej = C.take<int32_t>(nc), s_nvio = C.take<int32_t>(nc);
+  const auto s_kept = C.take<uint8_t>(nvs);
+  const auto s_prio = C.take<int32_t>(nvs);
+  const auto s_start = C.take<int64_t>(nvs);
+  const PickTail t = pick_tail(C, n_candidates, max_seg);
+  if (int rc = e->pick_buf.ensure(C.words())) return rc;
   int64_t* b = e->pick_buf.p;
-  HIP_TRY(hipMemcpyAsync(b + o_off, victim_offsets, (nc + 1) * 8, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + o_nodes, node_idx, nc * 4, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + o_rej, reject, nc * 4, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(b + o_nvio, num_violating, nc * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(s_off.at(b), victim_offsets, (nc + 1) * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(s_nodes.at(b), node_idx, nc * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(s_rej.at(b), reject, nc * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(s_nvio.at(b), num_violating, nc * 4, hipMemcpyHostToDevice, e->stream));
   if (nv > 0) {
-    HIP_TRY(hipMemcpyAsync(b + o_kept, kept, (size_t)nv, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(b + o_prio, victim_priority, (size_t)nv * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(b + o_start, victim_start_unix_nano, (size_t)nv * 8, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(s_kept.at(b), kept, (size_t)nv, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(s_prio.at(b), victim_priority, (size_t)nv * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(s_start.at(b), victim_start_unix_nano, (size_t)nv * 8, hipMemcpyHostToDevice, e->stream));
   }
-  const PickDev D{reinterpret_cast<const int32_t*>(b + o_nodes), b + o_off, reinterpret_cast<const int32_t*>(b + o_rej),
-                  reinterpret_cast<const uint8_t*>(b + o_kept), reinterpret_cast<const int32_t*>(b + o_nvio),
-                  reinterpret_cast<const int32_t*>(b + o_prio), b + o_start, b + o_tail};
-  return pick_run(e, n_candidates, max_seg, D, out_pick, out_victims);
+  const PickDev D{s_nodes.at(b), s_off.at(b), s_rej.at(b), s_kept.at(b), s_nvio.at(b), s_prio.at(b), s_start.at(b)};
+  return pick_run(e, n_candidates, max_seg, D, t, b, out_pick, out_victims);
 }
 
 // (added within ABI 18) the dry run and the pick in one call: select_victims — the kernel kg_pods_select_victims
@@ -8091,32 +8103,27 @@ int kg_pods_preempt(kg_engine* e, const kg_pod* pod, int64_t n_candidates, const
     return fail(KG_E_INVALID, "victims_cap %lld below the longest candidate segment %lld", (long long)victims_cap,
                 (long long)max_seg);
   if (max_seg > 0 && !out_victims) return fail(KG_E_INVALID, "null argument");
-  DevPod d;
-  RsvPod rp;
-  RsvSel rs;
-  int64_t rq[kAux];
+  LonePod lp;  // lives until the stream is synchronised
   std::vector<Victim> hv;
   PreExt X;
-  if (int rc = preempt_prepare(e, pod, victims, victim_slot, victim_minors, nv, d, rp, rs, rq, hv, X)) return rc;
-  auto words = [](size_t bytes) { return (bytes + 7) / 8; };
+  if (int rc = preempt_prepare(e, pod, victims, victim_slot, victim_minors, nv, lp, hv, X)) return rc;
   const size_t nvs = (size_t)std::max<int64_t>(nv, 1);
-  const size_t t_prio = 0, t_start = t_prio + words(nvs * 4), t_tail = t_start + nvs;
-  DryRunLayout L;
-  if (int rc = dry_run_launch(e, e->pick_buf, t_tail + pick_tail_words(n_candidates, max_seg), n_candidates, node_idx,
-                              victim_offsets, nv, pdb_violating, d, rp, rs, rq, hv, X, L))
-    return rc;
+  Carver C;
+  const DryRunLayout L = dry_run_layout(C, n_candidates, nv, hv.size());
+  const auto s_prio = C.take<int32_t>(nvs);
+  const auto s_start = C.take<int64_t>(nvs);
+  const PickTail t = pick_tail(C, n_candidates, max_seg);
+  if (int rc = e->pick_buf.ensure(C.words())) return rc;
   int64_t* b = e->pick_buf.p;
+  if (int rc = dry_run_launch(e, b, L, n_candidates, node_idx, victim_offsets, nv, pdb_violating, lp, hv, X)) return rc;
   if (nv > 0) {
-    HIP_TRY(hipMemcpyAsync(b + L.end + t_prio, victim_priority, (size_t)nv * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(b + L.end + t_start, victim_start_unix_nano, (size_t)nv * 8, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(s_prio.at(b), victim_priority, (size_t)nv * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(s_start.at(b), victim_start_unix_nano, (size_t)nv * 8, hipMemcpyHostToDevice, e->stream));
   }
   if (out_reject)
-    HIP_TRY(hipMemcpyAsync(out_reject, b + L.o_rej, (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
-  const PickDev D{reinterpret_cast<const int32_t*>(b + L.o_nodes), b + L.o_off,
-                  reinterpret_cast<const int32_t*>(b + L.o_rej), reinterpret_cast<const uint8_t*>(b + L.o_out),
-                  reinterpret_cast<const int32_t*>(b + L.o_nvio), reinterpret_cast<const int32_t*>(b + L.end + t_prio),
-                  b + L.end + t_start, b + L.end + t_tail};
-  return pick_run(e, n_candidates, max_seg, D, out_pick, out_victims);
+    HIP_TRY(hipMemcpyAsync(out_reject, L.rej.at(b), (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
+  const PickDev D{L.nodes.at(b), L.off.at(b), L.rej.at(b), L.out.at(b), L.nvio.at(b), s_prio.at(b), s_start.at(b)};
+  return pick_run(e, n_candidates, max_seg, D, t, b, out_pick, out_victims);
 }
 
 int kg_results_fetch_reservations(kg_engine* e, int64_t first, int64_t count, int32_t* out_slot) {

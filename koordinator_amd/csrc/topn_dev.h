@@ -21,23 +21,14 @@
 
 constexpr int kTopnFinalThreads = 1024;  // 16 waves over ≤ nb · KG_TOPN_MAX candidates
 
-// the one pod of the call, in the call's scratch (not the staged queue's records)
-struct TopnPod {
-  const DevPod* __restrict__ pod;
-  const RsvPod* __restrict__ rpod;
-  const DsPod* __restrict__ dpod;    // nullptr: no DeviceShare in the profile
-  const NumaPod* __restrict__ npod;  // nullptr: no NodeNUMAResource in the profile
-  const int64_t* __restrict__ aux;   // nullptr: the pod requests no ephemeral-storage / scalar resource
-  const DefPod* __restrict__ df;     // nullptr: no upstream default plugin in the profile
-};
-
 // header of the call's output buffer, copied back with the rows in one transfer
 struct TopnHdr {
   int64_t n_rows, feasible;
 };
 
 __global__ __launch_bounds__(kRsvThreads) void topn_eval(DevTable T, const RsvNode* __restrict__ RN,
-                                                         const int32_t* __restrict__ rsv_n, TopnPod tp, int64_t n,
+                                                         const int32_t* __restrict__ rsv_n,
+                                                         const LonePod* __restrict__ lp, uint32_t on, int64_t n,
                                                          EvalParams P, RsvParams RP, RsvExt X,
                                                          uint64_t* __restrict__ val, uint64_t* __restrict__ part) {
   __shared__ uint64_t s_red[kRsvThreads / kWave];
@@ -45,7 +36,8 @@ __global__ __launch_bounds__(kRsvThreads) void topn_eval(DevTable T, const RsvNo
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint64_t v = 0, pk = 0, rawv = 0, dsv = 0, tv = 0, av = 0;
   if (i < n) {
-    const RsvOut o = rsv_eval_node(T, RN, rsv_n, i, *tp.pod, *tp.rpod, P, RP, X, tp.dpod, tp.npod, nullptr, tp.aux, tp.df);
+    const LoneArgs a = lone_args(*lp, on, X);
+    const RsvOut o = rsv_eval_node(T, RN, rsv_n, i, lp->pod, lp->rpod, P, RP, a.X, a.dpod, a.npod, nullptr, a.aux, a.df);
     if (o.feas) {
       v = rsv_pack(o);
       pk = rsv_pref_key(o, (uint32_t)i);
@@ -141,7 +133,8 @@ __global__ __launch_bounds__(kTopnFinalThreads) void topn_final(const uint64_t* 
 
 // `en` = bit KG_PL_*: the plugin is enabled at Score in the profile (the others' columns are -1)
 __global__ __launch_bounds__(kWave) void topn_gather(DevTable T, const RsvNode* __restrict__ RN,
-                                                     const int32_t* __restrict__ rsv_n, TopnPod tp, int nb,
+                                                     const int32_t* __restrict__ rsv_n,
+                                                     const LonePod* __restrict__ lp, uint32_t on, int nb,
                                                      EvalParams P, RsvParams RP, RsvExt X,
                                                      const uint64_t* __restrict__ part,
                                                      const uint64_t* __restrict__ win,
@@ -160,7 +153,8 @@ __global__ __launch_bounds__(kWave) void topn_gather(DevTable T, const RsvNode* 
   const uint64_t key = win[r];
   const int64_t i = (int64_t)key_node(key);
   RsvDbg d;
-  const RsvOut o = rsv_eval_node(T, RN, rsv_n, i, *tp.pod, *tp.rpod, P, RP, X, tp.dpod, tp.npod, &d, tp.aux, tp.df);
+  const LoneArgs a = lone_args(*lp, on, X);
+  const RsvOut o = rsv_eval_node(T, RN, rsv_n, i, lp->pod, lp->rpod, P, RP, a.X, a.dpod, a.npod, &d, a.aux, a.df);
   kg_topn_row row;
   row.node_idx = (int32_t)i;
   row.nominated = o.feas ? o.nom : -1;
