@@ -31,6 +31,7 @@
 #include "kernels.h"
 #include "numa_dev.h"
 #include "ds_dev.h"
+#include "round_ctl.h"
 #include "rsv_dev.h"
 
 using namespace kg;
@@ -57,7 +58,6 @@ constexpr int kR = 8;                 // candidates kept per (pod, tile)
 constexpr int kRG = KG_GROUP_KEYS;    // (r5) candidates kept per (pod, tile group of kEW tiles): the merge's input
 static_assert(kRG % 2 == 0 && kRG <= kR, "group lists: an even count of at most kR keys");
 constexpr int kEvalWaves = 4;         // waves (tiles) per eval block
-constexpr int kMaxB = 64;             // modified rows are held one per lane of the resolver wave
 constexpr int kC = 64;                // merged candidates per pod (> any modified-set size: kC > kMaxB - 1)
 constexpr int kStaged = 3;            // hoisted rows of each pod's best candidates shipped with its record
 constexpr int kRecRows = 72;          // record layout (uint64 words): [0,kC) keys, [kC] ub, [72, 72+3·17) rows
@@ -65,8 +65,7 @@ constexpr int kCandStride = 128;      // per-pod record: 1 KiB (a 16-B multiple,
 constexpr int kMergeThreads = 256;
 constexpr int kMergeChunks = 4;       // chunks of 8 keys per merge thread: ≤ 1024 tile lists = 262144 nodes per rank
 constexpr double kAlgoBytesPerNode = 76.0;  // SURVEY §8(d) b_node for C1-C3: Fit 56 B + LoadAware 20 B
-constexpr int64_t kMaxBatchRounds = 256;
-constexpr int64_t kSpinLimit = 1 << 25;  // resolver chain wait: ~2 s of s_sleep(2) before reporting an error  // rounds launched between two host synchronisations
+constexpr int64_t kMaxBatchRounds = 256;  // rounds launched between two host synchronisations
 constexpr int64_t kMaxNodes = 1 << 19;  // resolver LDS: N/8-byte bitmap (≤ 64 KiB) + the round's records (≤ 64 KiB)
 static_assert(kRecRows + kStaged * kEvalRowWords <= kCandStride, "record layout");
 
@@ -914,39 +913,8 @@ __global__ __launch_bounds__(kWave * 4) void merge_wave(DevTable T, EvalParams P
 // prefetched word is patched with pod j's winner).  Rows of earlier rounds are loaded once, after the chain wait;
 // a node listed by two earlier rounds keeps its first slot (LDS hash), the duplicate becomes an infeasible hole.
 // Writes out_keys[first + j] (0 = unschedulable), the touched rows back to the table and into this round's
-// modified-row list (modlists[slot]), and advances the cursor ctl[0].
-constexpr int kMaxDepth = 4;          // pipelined rounds in flight (streams)
-constexpr int kMaxMod = 2 * kWave;    // modified-row slots: two register banks
-constexpr int kModHash = 512;         // node → slot hash for de-duplicating earlier rounds' lists
-constexpr int kModListStride = 1 + kMaxB;  // [count, node ids...] per round slot
-
-__device__ __forceinline__ uint32_t mod_hash(uint32_t node) { return (node * 2654435761u) >> (32 - 9); }
-static_assert(kModHash == 512, "hash width");
-
-// insert node → slot; returns the slot already holding node when present
-__device__ __forceinline__ int mod_insert(uint32_t* h, uint32_t node, int slot) {
-  const uint32_t v = ((node + 1u) << 8) | (uint32_t)slot;
-  uint32_t i = mod_hash(node);
-  for (int it = 0; it < kModHash; ++it) {
-    const uint32_t prev = atomicCAS(&h[i], 0u, v);
-    if (prev == 0u) return slot;
-    if ((prev >> 8) == node + 1u) return (int)(prev & 0xFFu);
-    i = (i + 1u) & (kModHash - 1);
-  }
-  return -1;
-}
-
-// End of a resolver: every store of this wave visible device-wide, then ctl[4] = seq (agent-scope release) for
-// the next round's resolver, which may already be resident on another round stream.
-// (r5) Release only (the guide's producer form): this wave's stores drained, the XCD L2 written back, the wait after
-// the write-back kept by inline asm (the compiler may drop it), then a relaxed flag store.  The acq_rel
-// __threadfence() it replaces also invalidated the L2 — a cost on the serial chain that nothing after it needs.
-__device__ __forceinline__ void publish_round(int64_t* ctl, int64_t seq) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (threadIdx.x == 0) __hip_atomic_store(&ctl[4], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// modified-row list (modlists[slot]), and advances the cursor ctl[CTL_CURSOR].
+// The control words and the chain steps (wait, abort, lists, close, publish) are defined in round_ctl.h.
 
 // exact key of one modified row for pod p (0 = filtered out).  A row outside eval_fast's domain takes the
 // reference-shaped eval_node with the EvalParams copy in LDS behind an opaque pointer: its runtime weight / flag
@@ -1180,43 +1148,24 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
     for (int w = lane; w < kModHash / 4; w += kWave) h4[w] = make_uint4(0, 0, 0, 0);
   }
   // Chain on the previous round's resolver (another round stream): its rows, cursor, poison and modified-row
-  // list are published with an agent-scope release of ctl[4] = its sequence number.  Bounded spin: a missing
+  // list are published with an agent-scope release of ctl[CTL_SEQ] = its sequence number.  Bounded spin: a missing
   // predecessor reports an error instead of hanging the device.
-  int timed_out = 0;
-  if (wait) {
-    if (lane == 0) {
-      int64_t it = 0;
-      while (__hip_atomic_load(&ctl[4], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq - 1) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++it > kSpinLimit) {
-          timed_out = 1;
-          break;
-        }
-      }
-    }
-    timed_out = __builtin_amdgcn_readfirstlane(timed_out);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  }
+  const int timed_out = __builtin_amdgcn_readfirstlane(lane == 0 ? chain_wait(ctl, seq, wait) : 0);
+  if (wait) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   KG_STAMP(2, 1);
   // the period decomposition's resolver time: from the predecessor's hand-off (modified-row loads included)
   const uint64_t t_active = __builtin_amdgcn_s_memrealtime();
-  if (timed_out || *poison || ctl[0] != first) {
+  if (round_stale(ctl, poison, first, timed_out)) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMA lands before the wave retires
-    if (lane == 0 && timed_out) ctl[5] = 1;
-    publish_round(ctl, seq);
+    round_abort(ctl, seq, timed_out);
     return;
   }
   // rows the n_prev previous rounds modified: slots [0, nM) of the register banks (slot s: lane s % 64, bank s / 64)
   ModRow R0, R1;
   mod_row_init(R0);
   mod_row_init(R1);
-  int nM = 0;
-  for (int d = 1; d <= n_prev; ++d) {  // concatenate the lists in LDS, then slot s → lane s % 64, bank s / 64
-    const int32_t* ml = modlists + (size_t)(((slot - d) % depth + depth) % depth) * kModListStride;
-    const int c = ml[0];
-    for (int t = lane; t < c; t += kWave) s_prevn[nM + t] = (uint32_t)ml[1 + t];
-    nM += c;
-  }
+  // the lists concatenated in LDS, then slot s → lane s % 64, bank s / 64
+  int nM = gather_prev_lists(modlists, slot, depth, n_prev, s_prevn, lane, true);
   __syncthreads();
   if (lane < nM) {
     const uint32_t node = s_prevn[lane];
@@ -1352,20 +1301,12 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
   const bool mine = lane < consumed && my_out != 0;
   const uint32_t my_node = mine ? key_node(my_out) : kNoNode;
   if (mine) writeback_pod(table_at(T0), my_node, s_pods[lane], paux + (size_t)(first + lane) * kAux);
-  int32_t* my_mod = modlists + (size_t)slot * kModListStride;
-  const uint64_t lane_lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  const uint64_t bm = __ballot(mine);
-  if (mine) my_mod[1 + __popcll(bm & lane_lt)] = (int32_t)my_node;
+  publish_mod_list(modlists, slot, mine, my_node, lane);
   if (lane < consumed) out_keys[first + lane] = my_out;
   if (QUOTA) quota_store(quotas, nq, lane, ql);
   if (lane == 0) {
-    my_mod[0] = __popcll(bm);
-    ctl[0] = first + consumed;
-    ctl[1] += 1;
-    ctl[2] += consumed;
-    ctl[6] += n_slow;  // diagnostics: pods that re-scored modified rows
-    if (consumed < nb) *poison = 1;
-    ctl[8] += (int64_t)(__builtin_amdgcn_s_memrealtime() - t_active);
+    ctl[CTL_SLOW] += n_slow;  // diagnostics: pods that re-scored modified rows
+    round_close(ctl, poison, first, consumed, nb, t_active);
   }
   publish_round(ctl, seq);
   KG_STAMP(2, 31);
@@ -1538,33 +1479,14 @@ __global__ __launch_bounds__(kMwThreads) void resolve_mw(DevTable T0, const DevP
   }
   // chain on the previous round's resolver (as resolve_round)
   if (wave == 0) {
-    int timed_out = 0;
-    if (wait) {
-      if (lane == 0) {
-        int64_t it = 0;
-        while (__hip_atomic_load(&ctl[4], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq - 1) {
-          __builtin_amdgcn_s_sleep(1);
-          if (++it > kSpinLimit) {
-            timed_out = 1;
-            break;
-          }
-        }
-      }
-      timed_out = __builtin_amdgcn_readfirstlane(timed_out);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
+    const int timed_out = __builtin_amdgcn_readfirstlane(lane == 0 ? chain_wait(ctl, seq, wait) : 0);
+    if (wait) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     KG_STAMP(2, 1);
-    const int abort_ = timed_out || *poison || ctl[0] != first;
-    if (abort_ && lane == 0 && timed_out) ctl[5] = 1;
-    int nM = 0;
-    if (!abort_) {  // rows the n_prev previous rounds modified: slots [0, nP), rows read after the chain wait
-      for (int d = 1; d <= n_prev; ++d) {
-        const int32_t* ml = modlists + (size_t)(((slot - d) % depth + depth) % depth) * kModListStride;
-        const int c = ml[0];
-        for (int t = lane; t < c; t += kWave) s_prevn[nM + t] = (uint32_t)ml[1 + t];
-        nM += c;
-      }
-    }
+    // the abort is carried to the other waves in LDS and published after the barrier below, so no round_abort here
+    const int abort_ = round_stale(ctl, poison, first, timed_out);
+    if (abort_ && lane == 0 && timed_out) ctl[CTL_ERROR] = 1;
+    // rows the n_prev previous rounds modified: slots [0, nP), rows read after the chain wait
+    const int nM = abort_ ? 0 : gather_prev_lists(modlists, slot, depth, n_prev, s_prevn, lane, true);
     __builtin_amdgcn_wave_barrier();
     for (int s = lane; s < nM; s += kWave) {
       const uint32_t node = s_prevn[s];
@@ -1930,26 +1852,18 @@ __global__ __launch_bounds__(kMwThreads) void resolve_mw(DevTable T0, const DevP
   const bool mine = !err && lane < consumed && my_out != 0;
   const uint32_t my_node = mine ? key_node(my_out) : kNoNode;
   if (mine) writeback_pod(table_at(T0), my_node, s_pods[lane], paux + (size_t)(first + lane) * kAux);
-  int32_t* my_mod = modlists + (size_t)slot * kModListStride;
-  const uint64_t lane_lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  const uint64_t bm = __ballot(mine);
-  if (mine) my_mod[1 + __popcll(bm & lane_lt)] = (int32_t)my_node;
+  publish_mod_list(modlists, slot, mine, my_node, lane);
   if (!err && lane < consumed) out_keys[first + lane] = my_out;
   if (QUOTA && !err) quota_store(quotas, nq, lane, ql);
   if (lane == 0) {
-    my_mod[0] = __popcll(bm);
     if (err) {
-      ctl[5] = 1;  // reported as a device error by the host
+      ctl[CTL_ERROR] = 1;  // reported as a device error by the host, which then reads no other word
       *poison = 1;
     } else {
-      ctl[0] = first + consumed;
-      ctl[1] += 1;
-      ctl[2] += consumed;
-      ctl[6] += n_slow;  // diagnostics: pods that re-scored recent winners on the chain
-      ctl[7] += n_wait;  // diagnostics: pods the chain waited for its helper
-      if (consumed < nb) *poison = 1;
+      ctl[CTL_SLOW] += n_slow;  // diagnostics: pods that re-scored recent winners on the chain
+      ctl[CTL_HELPER_WAITS] += n_wait;  // diagnostics: pods the chain waited for its helper
+      round_close(ctl, poison, first, consumed, nb, t_active);
     }
-    ctl[8] += (int64_t)(__builtin_amdgcn_s_memrealtime() - t_active);
   }
   publish_round(ctl, seq);
   KG_STAMP(2, 31);
@@ -2087,25 +2001,11 @@ __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTabl
   for (int w = lane; w < bitmap_words; w += kWave) bitmap[w] = 0;
   __syncthreads();
   // (r5) pipelined rounds: chain on the previous round's resolver (its rows, cursor, poison and winner list are
-  // published with a release of ctl[4] = its sequence number); bounded spin, as resolve_round
-  int timed_out = 0;
-  if (wait) {
-    if (lane == 0) {
-      int64_t it = 0;
-      while (__hip_atomic_load(&ctl[4], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq - 1) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++it > kSpinLimit) {
-          timed_out = 1;
-          break;
-        }
-      }
-    }
-    timed_out = __builtin_amdgcn_readfirstlane(timed_out);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  }
-  if (timed_out || *poison || ctl[0] != first) {
-    if (lane == 0 && timed_out) ctl[5] = 1;
-    publish_round(ctl, seq);
+  // published with a release of ctl[CTL_SEQ] = its sequence number); bounded spin, as resolve_round
+  const int timed_out = __builtin_amdgcn_readfirstlane(lane == 0 ? chain_wait(ctl, seq, wait) : 0);
+  if (wait) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (round_stale(ctl, poison, first, timed_out)) {
+    round_abort(ctl, seq, timed_out);
     return;
   }
   const uint64_t t_active = __builtin_amdgcn_s_memrealtime();  // the period decomposition's resolver time
@@ -2122,25 +2022,8 @@ __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTabl
   int nM = 0, consumed = 0;
   {  // the rows the n_prev earlier rounds modified (snapshot-stale: NUMA is not monotone, so every modified row is
      // re-scored for every pod anyway): de-duplicated into slots [0, nM), read after the chain wait
-    int n = 0;
-    for (int d = 1; d <= n_prev; ++d) {
-      const int32_t* ml = modlists + (size_t)(((slot - d) % depth + depth) % depth) * kModListStride;
-      const int c = ml[0];
-      for (int t = lane; t < c; t += kWave) s_prevn[n + t] = (uint32_t)ml[1 + t];
-      n += c;
-    }
-    __syncthreads();
-    const uint32_t node = lane < n ? s_prevn[lane] : 0xFFFFFFFFu;
-    bool dup = false;
-    for (int k = 0; k < n; ++k) dup |= lane > k && node == (uint32_t)__builtin_amdgcn_readlane((int)node, k);
-    const bool keep = lane < n && !dup;
-    const uint64_t km = __ballot(keep);
-    const uint64_t lane_lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const int sl = __popcll(km & lane_lt);
-    __syncthreads();
-    if (keep) s_prevn[sl] = node;
-    __syncthreads();
-    nM = __popcll(km);
+    const int n = gather_prev_lists(modlists, slot, depth, n_prev, s_prevn, lane, true);
+    nM = compact_prev_nodes(s_prevn, n, lane, true);
     if (lane < nM) {
       midx = s_prevn[lane];
       mrow = load_row(T, midx);
@@ -2273,21 +2156,9 @@ __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTabl
   }
   if (lane < consumed) out_keys[first + lane] = my_out;
   quota_store(quotas, nq, lane, ql);
-  {  // this round's modified rows (its placed pods' nodes; duplicates allowed) for the next rounds
-    const bool mine = lane < consumed && my_out != 0;
-    const uint64_t bm = __ballot(mine);
-    const uint64_t lane_lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    int32_t* my_mod = modlists + (size_t)slot * kModListStride;
-    if (mine) my_mod[1 + __popcll(bm & lane_lt)] = (int32_t)key_node(my_out);
-    if (lane == 0) my_mod[0] = __popcll(bm);
-  }
-  if (lane == 0) {
-    ctl[0] = first + consumed;
-    ctl[1] += 1;
-    ctl[2] += consumed;
-    if (consumed < nb) *poison = 1;
-    ctl[8] += (int64_t)(__builtin_amdgcn_s_memrealtime() - t_active);
-  }
+  // this round's modified rows (its placed pods' nodes) for the next rounds
+  publish_mod_list(modlists, slot, lane < consumed && my_out != 0, key_node(my_out), lane);
+  if (lane == 0) round_close(ctl, poison, first, consumed, nb, t_active);
   publish_round(ctl, seq);
 }
 
@@ -2363,26 +2234,15 @@ __global__ __launch_bounds__(kNuma2Threads) void resolve_round_numa2(DevTable T,
   if (tid < 16) s_c[tid] = 0;
   __syncthreads();
   if (tid == 0) {  // (r5) pipelined rounds: chain on the previous round's resolver (bounded spin, as resolve_round)
-    int timed_out = 0;
-    if (wait) {
-      int64_t it = 0;
-      while (__hip_atomic_load(&ctl[4], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < seq - 1) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++it > kSpinLimit) {
-          timed_out = 1;
-          break;
-        }
-      }
-    }
+    const int timed_out = chain_wait(ctl, seq, wait);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     s_c[4] = timed_out;
-    s_c[5] = (timed_out || *poison || ctl[0] != first) ? 1 : 0;
+    s_c[5] = round_stale(ctl, poison, first, timed_out) ? 1 : 0;
   }
   __syncthreads();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   if (s_c[5]) {
-    if (tid == 0 && s_c[4]) ctl[5] = 1;
-    publish_round(ctl, seq);
+    round_abort(ctl, seq, s_c[4]);
     return;
   }
   const uint64_t t_active = __builtin_amdgcn_s_memrealtime();
@@ -2407,27 +2267,9 @@ __global__ __launch_bounds__(kNuma2Threads) void resolve_round_numa2(DevTable T,
   NumaView* s_view = reinterpret_cast<NumaView*>(s_vieww);
   // the rows the n_prev earlier rounds modified, de-duplicated into slots [0, nM) by wave 0 (as resolve_round_numa)
   {
-    int n = 0;
-    for (int d = 1; d <= n_prev; ++d) {
-      const int32_t* ml = modlists + (size_t)(((slot - d) % depth + depth) % depth) * kModListStride;
-      const int c = ml[0];
-      if (wave == 0)
-        for (int t = lane; t < c; t += kWave) s_prevn[n + t] = (uint32_t)ml[1 + t];
-      n += c;
-    }
-    __syncthreads();
-    const uint32_t node = (wave == 0 && lane < n) ? s_prevn[lane] : 0xFFFFFFFFu;
-    bool dup = false;
-    if (wave == 0)
-      for (int k = 0; k < n; ++k) dup |= lane > k && node == (uint32_t)__builtin_amdgcn_readlane((int)node, k);
-    const bool keep = wave == 0 && lane < n && !dup;
-    const uint64_t km = __ballot(keep);
-    const uint64_t lane_lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    __syncthreads();
-    if (keep) s_prevn[__popcll(km & lane_lt)] = node;
-    __syncthreads();
+    const int n = gather_prev_lists(modlists, slot, depth, n_prev, s_prevn, lane, wave == 0);
+    const int nM0 = compact_prev_nodes(s_prevn, n, lane, wave == 0);
     if (wave == 0) {
-      const int nM0 = __popcll(km);
       if (lane < nM0) {
         const uint32_t m = s_prevn[lane];
         s_node[lane] = m;
@@ -2676,19 +2518,8 @@ __global__ __launch_bounds__(kNuma2Threads) void resolve_round_numa2(DevTable T,
     }
     if (lane < consumed) out_keys[first + lane] = my_out;
     quota_store(quotas, nq, lane, ql);
-    const bool mine = lane < consumed && my_out != 0;
-    const uint64_t bm = __ballot(mine);
-    const uint64_t lane_lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    int32_t* my_mod = modlists + (size_t)slot * kModListStride;
-    if (mine) my_mod[1 + __popcll(bm & lane_lt)] = (int32_t)key_node(my_out);
-    if (lane == 0) {
-      my_mod[0] = __popcll(bm);
-      ctl[0] = first + consumed;
-      ctl[1] += 1;
-      ctl[2] += consumed;
-      if (consumed < nb) *poison = 1;
-      ctl[8] += (int64_t)(__builtin_amdgcn_s_memrealtime() - t_active);
-    }
+    publish_mod_list(modlists, slot, lane < consumed && my_out != 0, key_node(my_out), lane);
+    if (lane == 0) round_close(ctl, poison, first, consumed, nb, t_active);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -2734,7 +2565,7 @@ __global__ void scatter_numa(NumaTable NT, const NumaStatic* __restrict__ s, con
 //   merge_round    — as for the other profiles
 //   resolve_round_ds — FIFO replay; pod j keeps M_j = M only if an unmodified node or a modified row still holds
 //                    M (counts of round-start holders among the modified rows); otherwise the round ends there.
-// Rounds are unpipelined and driven by the device cursor: every kernel reads its first pod from ctl[0], so an
+// Rounds are unpipelined and driven by the device cursor: every kernel reads its first pod from ctl[CTL_CURSOR], so an
 // early stop just makes the next round start at the cursor (no poison, no host round trip).
 constexpr int kDsPpw = 8;
 
@@ -2743,7 +2574,7 @@ struct DsTable {
 };
 
 __device__ __forceinline__ bool ds_round_range(const int64_t* ctl, int64_t end, int B, int64_t& first, int& nb) {
-  first = ctl[0];
+  first = ctl[CTL_CURSOR];
   const int64_t left = end - first;
   nb = left < B ? (int)left : B;
   return nb > 0;
@@ -3132,12 +2963,7 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
     for (int w = lane; w < nq * (int)(sizeof(QuotaRow) / 8); w += kWave) qw[w] = sq[w];
   }
   __threadfence();
-  if (lane == 0) {
-    ctl[0] = first + consumed;
-    ctl[1] += 1;
-    ctl[2] += consumed;
-    ctl[8] += (int64_t)(__builtin_amdgcn_s_memrealtime() - t_active);
-  }
+  if (lane == 0) round_close<false>(ctl, nullptr, first, consumed, nb, t_active);
 }
 
 // kg_pods_evaluate_device: DeviceShare Filter + raw Score of one pod on every node (the plugin alone)
@@ -3859,6 +3685,45 @@ struct Carver {
   size_t words() const { return n; }
 };
 
+// The launch arguments a captured graph bakes in, as bytes in the order they are put.
+struct GraphSig {
+  std::vector<unsigned char> bytes;
+  template <typename T>
+  void put(const T& v) {
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(&v);
+    bytes.insert(bytes.end(), b, b + sizeof(T));
+  }
+};
+
+// An instantiated hipGraph, reused while the launch arguments it was captured with are unchanged.
+struct GraphCache {
+  hipGraphExec_t exec = nullptr;
+  std::vector<unsigned char> sig;
+  void reset() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    exec = nullptr;
+  }
+  // capture_fn issues the graph's launches on `stream`; `what` names the graph in the error text
+  template <typename F>
+  int ensure(hipStream_t stream, const GraphSig& want, F&& capture_fn, const char* what) {
+    if (exec && want.bytes == sig) return 0;
+    reset();
+    hipGraph_t gr = nullptr;
+    HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    capture_fn();
+    const hipError_t ce = hipStreamEndCapture(stream, &gr);
+    if (ce != hipSuccess) return fail(KG_E_DEVICE, "hipStreamEndCapture: %s", hipGetErrorString(ce));
+    const hipError_t ie = hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(gr);
+    if (ie != hipSuccess) {
+      exec = nullptr;
+      return fail(KG_E_DEVICE, "%s: %s", what, hipGetErrorString(ie));
+    }
+    sig = want.bytes;
+    return 0;
+  }
+};
+
 int64_t bits_for(int64_t v) {
   int b = 1;
   while (b < 32 && (int64_t(1) << b) <= v) ++b;
@@ -3943,10 +3808,7 @@ struct kg_engine {
   DevBuf<uint64_t> gathered;  // [D][n_ranks][B][kCandStride] per-rank merged records (n_ranks > 1), by round slot
   DevBuf<uint64_t> cand;      // [D][B][kCandStride] final merged candidates, by round slot
   DevBuf<uint64_t> out_keys;
-  DevBuf<int64_t> cursor;     // [0] cursor, [1] rounds, [2] consumed, [3] poison (int32 in its low word),
-                              // [4] last published resolver sequence, [5] device error (chain wait timed out),
-                              // [6] pods re-scored on the chain, [7] chain waits on a helper, [8] resolver active
-                              // time (s_memrealtime ticks)
+  DevBuf<int64_t> cursor;     // [CTL_WORDS] the round engine's control block (round_ctl.h)
   DevBuf<int32_t> modlists;   // [kMaxDepth][kModListStride]: rows each round modified ([0] = count), by round slot
   DevBuf<uint32_t> tickets;   // (r5) [kMaxDepth][kMaxB]: fused-merge tickets per (round slot, pod group)
   // round r runs on rs[r % D] (eval → merge → [RCCL on comms[r % D]] → resolve); `stream` runs ingest
@@ -4008,12 +3870,10 @@ struct kg_engine {
   DevBuf<RsvSel> rsel;          // (ABI 12) [staged + kMaxB] reservation-affinity selectors (RsvPod::aux)
   DevBuf<int32_t> out_rslot;    // [staged + kMaxB]
   DevBuf<uint64_t> rsv_val;     // [capacity] packed per-node pass-1 values
-  DevBuf<unsigned long long> rsv_ws;  // [8]: [3] = pod cursor, [4] = the call's end (graph launches)
+  DevBuf<unsigned long long> rsv_ws;  // [WS_WORDS] the exact pass's and exact rounds' workspace (round_ctl.h)
   // the instantiated reservation group graph, reused while its launch arguments are unchanged
-  hipGraphExec_t rsv_exec = nullptr;   // a group of kRsvGroup passes + rsv_apply
-  std::vector<unsigned char> rsv_exec_sig;
-  hipGraphExec_t rsv_exec1 = nullptr;  // one pass + rsv_apply (single-pod calls)
-  std::vector<unsigned char> rsv_exec1_sig;
+  GraphCache rsv_exec;   // a group of kRsvGroup passes + rsv_apply
+  GraphCache rsv_exec1;  // one pass + rsv_apply (single-pod calls)
   DevBuf<uint64_t> rsv_part;    // [13][blocks] per-block partials (preferred-node key, max raw, max key, max ds raw,
                                 // max taint count, max affinity sum; (ABI 12) group_pre's min match / total, the
                                 // filtered-node count and the spread count / InterPodAffinity raw extremes)
@@ -4057,8 +3917,7 @@ struct kg_engine {
   DevBuf<uint64_t> xr_cand;     // [kXrPods][kCandStride]
   DevBuf<uint64_t> xr_norm_all; // (r5) [n_ranks][kXrPods][kXrNorm]: every rank's shard statistics (several ranks)
   DevBuf<uint64_t> xr_rec_all;  // (r5) [n_ranks][kXrPods][kCandStride]: every rank's merged record (several ranks)
-  hipGraphExec_t xr_exec = nullptr;  // kXrGraphRounds rounds
-  std::vector<unsigned char> xr_exec_sig;
+  GraphCache xr_exec;  // kXrGraphRounds rounds
   double xr_avg = kXrPods;      // pods a round consumed on average (sizes the launches between host checks)
   // live kernel timing (kg_profile_enable): HIP event pairs around every launch of the round runners, on the
   // launch's own stream, folded into per-kind totals after each batch synchronises
@@ -4933,7 +4792,7 @@ int profile_bits(const EvalParams& P) {
   }
 #endif
 
-int32_t* poison_ptr(kg_engine* e) { return reinterpret_cast<int32_t*>(e->cursor.p + 3); }
+int32_t* poison_ptr(kg_engine* e) { return reinterpret_cast<int32_t*>(e->cursor.p + CTL_POISON); }
 uint64_t* lists_slot(kg_engine* e, const RoundGeom& g, int slot) {
   return e->lists.p + (size_t)slot * g.B * g.nl_max * kR;
 }
@@ -5186,7 +5045,8 @@ int launch_merge(kg_engine* e, const RoundGeom& g, int nb, int slot, hipStream_t
 int run_batch(kg_engine* e, const RoundGeom& g, int64_t cur, int64_t end, int64_t n_rounds) {
   const int D = g.depth;
   const bool fuse = fused_merge(e, g);
-  HIP_TRY(hipMemsetAsync(e->cursor.p + 3, 0, 3 * 8, e->rs[0]));  // poison, resolver sequence, device error
+  // poison, resolver sequence, device error: adjacent words (round_ctl.h)
+  HIP_TRY(hipMemsetAsync(e->cursor.p + CTL_POISON, 0, (CTL_ERROR - CTL_POISON + 1) * 8, e->rs[0]));
   if (fuse) HIP_TRY(hipMemsetAsync(e->tickets.p, 0, (size_t)kMaxDepth * kMaxB * 4, e->rs[0]));
   if (D > 1) {  // the other round streams must not start before that reset
     HIP_TRY(hipEventRecord(e->ev_res[0], e->rs[0]));
@@ -5323,7 +5183,7 @@ double now_s() {
 
 
 // Reservation profile: one FIFO pod per device pass (rsv_eval → rsv_select; Reserve in the next rsv_eval),
-// kRsvGroup passes + the group-closing rsv_apply per hipGraph launch.  The pod index lives in the device cursor ws[3]; passes past `end` are no-ops.
+// kRsvGroup passes + the group-closing rsv_apply per hipGraph launch.  The pod index lives in the device cursor ws[WS_CURSOR]; passes past `end` are no-ops.
 constexpr int kRsvGroup = 32;
 constexpr int64_t kExactSmall = 2;  // schedule calls of at most this many pods take the exact pass (single-pod path)
 RsvExt rsv_ext(kg_engine* e) {
@@ -5393,7 +5253,9 @@ int run_rsv(kg_engine* e, int64_t first, int64_t count, kg_stats* stats, double 
     RsvExt X = rsv_ext(e);
     if (!e->dsx_q) X.dsx = nullptr;  // (r6) no RDMA / FPGA request staged: the lean rsv_eval variant (part of the graph key)
     const int rf = rsv_eval_flags(X);
-    const unsigned long long init[5] = {0, 0, 0, (unsigned long long)first, (unsigned long long)end};
+    unsigned long long init[WS_END + 1] = {};  // the words past the call's end stay as they are
+    init[WS_CURSOR] = (unsigned long long)first;
+    init[WS_END] = (unsigned long long)end;
     HIP_TRY(hipMemcpyAsync(e->rsv_ws.p, init, sizeof(init), hipMemcpyHostToDevice, e->stream));
     if (e->grp_on) {  // the zone sums start from zero (then each pod's rsv_select clears the next pod's)
       HIP_TRY(hipMemsetAsync(e->gz.p, 0, (size_t)2 * kZoneSumWords * 4, e->stream));
@@ -5429,36 +5291,17 @@ int run_rsv(kg_engine* e, int64_t first, int64_t count, kg_stats* stats, double 
     static const bool no_graph = std::getenv("KG_RSV_NO_GRAPH") && std::getenv("KG_RSV_NO_GRAPH")[0] == '1';
     // graphs of `passes` passes (kRsvGroup, or 1 for single-pod calls), keyed on their launch arguments (table /
     // buffer pointers, sizes, profile parameters) and re-instantiated when one changes
-    auto graph = [&](int passes, hipGraphExec_t& exec, std::vector<unsigned char>& exec_sig) -> int {
-      std::vector<unsigned char> sig;
-      auto put = [&](const void* q, size_t len) {
-        const unsigned char* b = static_cast<const unsigned char*>(q);
-        sig.insert(sig.end(), b, b + len);
-      };
-      put(&e->T, sizeof(e->T));
+    auto graph = [&](int passes, GraphCache& gc) -> int {
+      GraphSig sig;
+      sig.put(e->T);
       const void* ptrs[] = {e->rsv_d.p, e->rsv_nd.p, e->pods.p, e->rpods.p, e->rsv_val.p, e->rsv_part.p,
                             e->out_keys.p, e->out_rslot.p, e->rsv_ws.p};
-      put(ptrs, sizeof(ptrs));
-      put(&n, sizeof(n));
-      put(&e->P, sizeof(e->P));
-      put(&e->RP, sizeof(e->RP));
-      put(&X, sizeof(X));
-      if (exec && sig == exec_sig) return 0;
-      if (exec) (void)hipGraphExecDestroy(exec);
-      exec = nullptr;
-      hipGraph_t gr = nullptr;
-      HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-      issue_group(-1, passes);
-      const hipError_t ce = hipStreamEndCapture(e->stream, &gr);
-      if (ce != hipSuccess) return fail(KG_E_DEVICE, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-      const hipError_t ie = hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(gr);
-      if (ie != hipSuccess) {
-        exec = nullptr;
-        return fail(KG_E_DEVICE, "exact pass graph: %s", hipGetErrorString(ie));
-      }
-      exec_sig = sig;
-      return 0;
+      sig.put(ptrs);
+      sig.put(n);
+      sig.put(e->P);
+      sig.put(e->RP);
+      sig.put(X);
+      return gc.ensure(e->stream, sig, [&] { issue_group(-1, passes); }, "exact pass graph");
     };
     if (no_graph || e->prof_on || (count > 1 && count < kRsvGroup)) {
       for (int64_t c = 0; c < count; c += kRsvGroup) issue_group(end, (int)std::min<int64_t>(kRsvGroup, count - c));
@@ -5467,15 +5310,10 @@ int run_rsv(kg_engine* e, int64_t first, int64_t count, kg_stats* stats, double 
       if (e->prof_on)
         if (int rc = prof_collect(e)) return rc;
     } else {
-      hipGraphExec_t ex = nullptr;
-      if (count == 1) {
-        if (int rc = graph(1, e->rsv_exec1, e->rsv_exec1_sig)) return rc;
-        ex = e->rsv_exec1;
-      } else {
-        if (int rc = graph(kRsvGroup, e->rsv_exec, e->rsv_exec_sig)) return rc;
-        ex = e->rsv_exec;
-      }
+      GraphCache& gc = count == 1 ? e->rsv_exec1 : e->rsv_exec;
       const int64_t per = count == 1 ? 1 : kRsvGroup;
+      if (int rc = graph((int)per, gc)) return rc;
+      const hipGraphExec_t ex = gc.exec;
       hipError_t ge = hipSuccess;
       for (int64_t c = 0; ge == hipSuccess && c < count; c += per) ge = hipGraphLaunch(ex, e->stream);
       if (ge == hipSuccess) ge = hipStreamSynchronize(e->stream);
@@ -5516,7 +5354,9 @@ int run_xr(kg_engine* e, int64_t first, int64_t count, kg_stats* stats, double t
   const int nt = (int)((n + kTile - 1) / kTile);
   const int64_t stride = e->capacity;
   const RsvExt X = rsv_ext(e);
-  const unsigned long long init[8] = {0, 0, 0, (unsigned long long)first, (unsigned long long)end, 0, 0, 0};
+  unsigned long long init[WS_WORDS] = {};
+  init[WS_CURSOR] = (unsigned long long)first;
+  init[WS_END] = (unsigned long long)end;
   HIP_TRY(hipMemcpyAsync(e->rsv_ws.p, init, sizeof(init), hipMemcpyHostToDevice, e->stream));
   // (r5) several ranks: this rank's range of tiles (an empty range keeps one tile past the table: every node masked)
   const int R = e->n_ranks, tpr = (nt + R - 1) / R, tile_base = e->rank * tpr;
@@ -5529,7 +5369,7 @@ int run_xr(kg_engine* e, int64_t first, int64_t count, kg_stats* stats, double t
   const int xf = (X.ns ? XF_NUMA : 0) | (X.ds ? XF_DS : 0) | (X.defp ? XF_DEF : 0);
   const size_t lds = xr_resolve_lds_bytes(xf, X.nq, X.paux != nullptr, bitmap_words);
   if (lds > 160 * 1024) return fail(KG_E_UNSUPPORTED, "exact rounds: %zu B of LDS for %lld nodes", lds, (long long)n);
-  const int32_t* poison = reinterpret_cast<const int32_t*>(e->rsv_ws.p + 7);  // stays 0
+  const int32_t* poison = reinterpret_cast<const int32_t*>(e->rsv_ws.p + WS_ZERO);
   uint64_t* val = e->xr_val.p;
   uint32_t* val2 = e->def_score ? e->xr_val2.p : nullptr;
   uint32_t* affk = e->numa_on ? e->xr_aff.p : nullptr;
@@ -5585,47 +5425,31 @@ int run_xr(kg_engine* e, int64_t first, int64_t count, kg_stats* stats, double t
   };
   static const bool no_graph = std::getenv("KG_RSV_NO_GRAPH") && std::getenv("KG_RSV_NO_GRAPH")[0] == '1';
   if (!no_graph && !e->prof_on && R == 1) {  // the instantiated graph of kXrGraphRounds rounds, keyed on its launch arguments
-    std::vector<unsigned char> sig;
-    auto put = [&](const void* q, size_t len) {
-      const unsigned char* b = static_cast<const unsigned char*>(q);
-      sig.insert(sig.end(), b, b + len);
-    };
-    put(&e->T, sizeof(e->T));
+    GraphSig sig;
+    sig.put(e->T);
     const void* ptrs[] = {e->rsv_d.p, e->rsv_nd.p, e->pods.p, e->rpods.p, val, val2, affk, e->xr_part.p,
                           e->xr_norm_d.p, e->xr_lists.p, e->xr_cand.p, e->out_keys.p, e->out_rslot.p, e->rsv_ws.p};
-    put(ptrs, sizeof(ptrs));
-    put(&n, sizeof(n));
-    put(&e->P, sizeof(e->P));
-    put(&e->RP, sizeof(e->RP));
-    put(&X, sizeof(X));
-    if (!e->xr_exec || sig != e->xr_exec_sig) {
-      if (e->xr_exec) (void)hipGraphExecDestroy(e->xr_exec);
-      e->xr_exec = nullptr;
-      hipGraph_t gr = nullptr;
-      HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+    sig.put(ptrs);
+    sig.put(n);
+    sig.put(e->P);
+    sig.put(e->RP);
+    sig.put(X);
+    auto capture = [&] {
       for (int r = 0; r < kXrGraphRounds; ++r) (void)issue_round();
-      const hipError_t ce = hipStreamEndCapture(e->stream, &gr);
-      if (ce != hipSuccess) return fail(KG_E_DEVICE, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-      const hipError_t ie = hipGraphInstantiate(&e->xr_exec, gr, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(gr);
-      if (ie != hipSuccess) {
-        e->xr_exec = nullptr;
-        return fail(KG_E_DEVICE, "exact rounds graph: %s", hipGetErrorString(ie));
-      }
-      e->xr_exec_sig = sig;
-    }
+    };
+    if (int rc = e->xr_exec.ensure(e->stream, sig, capture, "exact rounds graph")) return rc;
   }
   int64_t cursor = first, launched = 0;
-  unsigned long long ws[8];
+  unsigned long long ws[WS_WORDS];
   while (cursor < end) {
     // rounds for the pods left at the recent rate (at least one graph), then one check of the cursor
     const double per = std::max(1.0, e->xr_avg);
     int64_t rounds = (int64_t)std::ceil((double)(end - cursor) / per);
     rounds = std::max<int64_t>(1, std::min<int64_t>(rounds, kMaxBatchRounds));
-    if (e->xr_exec && !e->prof_on && R == 1) {
+    if (e->xr_exec.exec && !e->prof_on && R == 1) {
       const int64_t graphs = (rounds + kXrGraphRounds - 1) / kXrGraphRounds;
       for (int64_t g = 0; g < graphs; ++g) {
-        const hipError_t ge = hipGraphLaunch(e->xr_exec, e->stream);
+        const hipError_t ge = hipGraphLaunch(e->xr_exec.exec, e->stream);
         if (ge != hipSuccess) return fail(KG_E_DEVICE, "exact rounds graph: %s", hipGetErrorString(ge));
       }
       rounds = graphs * kXrGraphRounds;
@@ -5639,15 +5463,15 @@ int run_xr(kg_engine* e, int64_t first, int64_t count, kg_stats* stats, double t
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->prof_on)
       if (int rc = prof_collect(e)) return rc;
-    const int64_t c = (int64_t)ws[3];
+    const int64_t c = (int64_t)ws[WS_CURSOR];
     if (c <= cursor) return fail(KG_E_DEVICE, "exact rounds made no progress at pod %lld", (long long)cursor);
     cursor = c;
-    if (ws[5] > 0) e->xr_avg = 0.5 * e->xr_avg + 0.5 * ((double)ws[6] / (double)ws[5]);
+    if (ws[WS_ROUNDS] > 0) e->xr_avg = 0.5 * e->xr_avg + 0.5 * ((double)ws[WS_CONSUMED] / (double)ws[WS_ROUNDS]);
   }
   if (stats) {
     std::memset(stats, 0, sizeof(*stats));
-    stats->device_batches = (int64_t)ws[5];
-    stats->node_evaluations = (int64_t)ws[5] * kXrPods * n;
+    stats->device_batches = (int64_t)ws[WS_ROUNDS];
+    stats->node_evaluations = (int64_t)ws[WS_ROUNDS] * kXrPods * n;
     stats->seconds = now_s() - t0;
   }
   (void)launched;
@@ -5933,7 +5757,7 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
   e->T.aux = e->cols64.p + 14 * cap;
   e->T.cap = cap;
   if (int rc = e->cursor.ensure(16)) return bail(rc);
-  if (hipMemsetAsync(e->cursor.p, 0, 16 * 8, e->stream) != hipSuccess) return bail(fail(KG_E_DEVICE, "hipMemset"));
+  if (hipMemsetAsync(e->cursor.p, 0, CTL_WORDS * 8, e->stream) != hipSuccess) return bail(fail(KG_E_DEVICE, "hipMemset"));
   if (int rc = e->modlists.ensure(kMaxDepth * kModListStride)) return bail(rc);
   if (hipMemsetAsync(e->modlists.p, 0, kMaxDepth * kModListStride * 4, e->stream) != hipSuccess) return bail(fail(KG_E_DEVICE, "hipMemset"));
   if (int rc = e->tickets.ensure(kMaxDepth * kMaxB)) return bail(rc);
@@ -6028,9 +5852,9 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
     if (int rc = e->rsv_nd.ensure(cap)) return bail(rc);
     if (int rc = e->rsv_pd.ensure((size_t)kRsvSlots * cap)) return bail(rc);
     if (int rc = e->rsv_val.ensure(cap)) return bail(rc);
-    if (int rc = e->rsv_ws.ensure(8)) return bail(rc);
+    if (int rc = e->rsv_ws.ensure(WS_WORDS)) return bail(rc);
     if (int rc = e->rsv_part.ensure(15 * ((cap + kRsvThreads - 1) / kRsvThreads) + 4)) return bail(rc);
-    if (hipMemsetAsync(e->rsv_nd.p, 0, cap * 4, e->stream) != hipSuccess || hipMemsetAsync(e->rsv_ws.p, 0, 64, e->stream) != hipSuccess ||
+    if (hipMemsetAsync(e->rsv_nd.p, 0, cap * 4, e->stream) != hipSuccess || hipMemsetAsync(e->rsv_ws.p, 0, WS_WORDS * 8, e->stream) != hipSuccess ||
         hipMemsetAsync(e->rsv_pd.p, 0, (size_t)kRsvSlots * cap * 8, e->stream) != hipSuccess)
       return bail(fail(KG_E_DEVICE, "hipMemset"));
   }
@@ -6272,12 +6096,9 @@ void kg_engine_destroy(kg_engine* e) {
   e->rpods.release();
   e->out_rslot.release();
   e->rsv_val.release();
-  if (e->rsv_exec) (void)hipGraphExecDestroy(e->rsv_exec);
-  e->rsv_exec = nullptr;
-  if (e->rsv_exec1) (void)hipGraphExecDestroy(e->rsv_exec1);
-  e->rsv_exec1 = nullptr;
-  if (e->xr_exec) (void)hipGraphExecDestroy(e->xr_exec);
-  e->xr_exec = nullptr;
+  e->rsv_exec.reset();
+  e->rsv_exec1.reset();
+  e->xr_exec.reset();
   e->xr_val.release();
   e->xr_val2.release();
   e->xr_aff.release();
@@ -6765,9 +6586,9 @@ static int schedule_staged_impl(kg_engine* e, int64_t first, int64_t count, kg_s
   RoundGeom g;
   if (int rc = prepare_rounds(e, g)) return rc;
   const int64_t end = first + count;
-  const int64_t init[16] = {first};
-  int64_t host_stats[16] = {first};
-  HIP_TRY(hipMemcpyAsync(e->cursor.p, init, 16 * 8, hipMemcpyHostToDevice, e->stream));
+  int64_t host_stats[CTL_WORDS] = {};
+  host_stats[CTL_CURSOR] = first;
+  HIP_TRY(hipMemcpyAsync(e->cursor.p, host_stats, sizeof(host_stats), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   int64_t cur = first;
   while (cur < end) {
@@ -6776,23 +6597,23 @@ static int schedule_staged_impl(kg_engine* e, int64_t first, int64_t count, kg_s
     // at most rounds_ahead rounds: halved towards the rounds that ran before a stop when rounds stop early (small
     // clusters), doubled back when a batch completes, so a stop wastes few poisoned launches.
     const int64_t n_rounds = std::min<int64_t>({(end - cur + g.B - 1) / g.B, kMaxBatchRounds, e->rounds_ahead});
-    const int64_t ran0 = host_stats[1];
+    const int64_t ran0 = host_stats[CTL_ROUNDS];
     if (int rc = e->ds_on ? run_batch_ds(e, g, end, n_rounds) : run_batch(e, g, cur, end, n_rounds)) return rc;
-    HIP_TRY(hipMemcpy(host_stats, e->cursor.p, 16 * 8, hipMemcpyDeviceToHost));
-    if (host_stats[5]) return fail(KG_E_DEVICE, "resolver chain wait timed out (round sequence %lld)", (long long)host_stats[4]);
-    const bool stopped = host_stats[0] < std::min<int64_t>(end, cur + n_rounds * g.B);
-    const int64_t ran = host_stats[1] - ran0;
+    HIP_TRY(hipMemcpy(host_stats, e->cursor.p, sizeof(host_stats), hipMemcpyDeviceToHost));
+    if (host_stats[CTL_ERROR]) return fail(KG_E_DEVICE, "resolver chain wait timed out (round sequence %lld)", (long long)host_stats[CTL_SEQ]);
+    const bool stopped = host_stats[CTL_CURSOR] < std::min<int64_t>(end, cur + n_rounds * g.B);
+    const int64_t ran = host_stats[CTL_ROUNDS] - ran0;
     if (!e->ds_on)  // DeviceShare rounds are cursor-driven: a stop never poisons the rest of the batch
       e->rounds_ahead = stopped ? std::max<int64_t>(2, std::min<int64_t>(e->rounds_ahead, 2 * ran))
                                 : std::min<int64_t>(kMaxBatchRounds, 2 * e->rounds_ahead);
-    cur = host_stats[0];
+    cur = host_stats[CTL_CURSOR];
   }
   if (stats) {
     std::memset(stats, 0, sizeof(*stats));
-    stats->device_batches = host_stats[1];
-    stats->reserved[0] = (double)host_stats[6];  // diagnostics: slow-path pods, speculation steps (resolve_round)
-    stats->reserved[1] = (double)host_stats[7];
-    stats->reserved[2] = (double)host_stats[8] * 1e-8;  // resolvers' active time (s_memrealtime, 100 MHz): after the
+    stats->device_batches = host_stats[CTL_ROUNDS];
+    stats->reserved[0] = (double)host_stats[CTL_SLOW];  // diagnostics: slow-path pods, speculation steps (resolve_round)
+    stats->reserved[1] = (double)host_stats[CTL_HELPER_WAITS];
+    stats->reserved[2] = (double)host_stats[CTL_ACTIVE_TICKS] * 1e-8;  // resolvers' active time (s_memrealtime, 100 MHz): after the
                                                          // chain wait to the publish, summed over the call's rounds
     stats->node_evaluations = count * g.N;
     stats->seconds = now_s() - t0;
@@ -7153,8 +6974,8 @@ static int bench_rsv(kg_engine* e, int which, int iters, double* avg_ms, double*
   int64_t with_slots = 0;
   for (int64_t i = 0; i < n; ++i) with_slots += hn[i] > 0;
   const unsigned blocks = (unsigned)((n + kRsvThreads - 1) / kRsvThreads);
-  const unsigned long long zero[4] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(e->rsv_ws.p, zero, 32, hipMemcpyHostToDevice, e->stream));
+  const unsigned long long zero[WS_CURSOR + 1] = {};  // the quota tag and the pod cursor
+  HIP_TRY(hipMemcpyAsync(e->rsv_ws.p, zero, sizeof(zero), hipMemcpyHostToDevice, e->stream));
   RsvExt X = rsv_ext(e);
   if (!e->dsx_q) X.dsx = nullptr;  // the variant run_rsv launches
   const int rf = rsv_eval_flags(X);
@@ -7183,7 +7004,7 @@ static int bench_rsv(kg_engine* e, int which, int iters, double* avg_ms, double*
   HIP_TRY(hipEventElapsedTime(&ms, a, b));
   (void)hipEventDestroy(a);
   (void)hipEventDestroy(b);
-  HIP_TRY(hipMemcpyAsync(e->rsv_ws.p, zero, 32, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->rsv_ws.p, zero, sizeof(zero), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (avg_ms) *avg_ms = ms / iters;
   // rsv_eval: the Fit/LoadAware columns, rsv_n and the packed value per node, the slot rows of nodes holding
@@ -7238,10 +7059,10 @@ int kg_bench_kernel(kg_engine* e, int which, int iters, double* avg_ms, double* 
     }
     return 0;
   };
-  static const int64_t zero4[6] = {0, 0, 0, 0, 0, 0};
+  static const int64_t ctl_reset[CTL_ERROR + 1] = {};  // cursor … device error; the diagnostic words keep counting
   const int nb = (int)end;
   if (int rc = snapshot(false)) return rc;
-  HIP_TRY(hipMemcpyAsync(e->cursor.p, zero4, 48, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->cursor.p, ctl_reset, sizeof(ctl_reset), hipMemcpyHostToDevice, e->stream));
   // one real round: valid lists and candidates to replay on
   if (int rc = e->ds_on ? launch_round_ds(e, g, end, e->stream) : run_batch(e, g, 0, end, 1)) return rc;
   HIP_TRY(hipGetLastError());
@@ -7251,7 +7072,7 @@ int kg_bench_kernel(kg_engine* e, int which, int iters, double* avg_ms, double* 
   HIP_TRY(hipEventCreate(&b));
   float total_ms = 0.f;
   for (int it = 0; it < iters; ++it) {
-    HIP_TRY(hipMemcpyAsync(e->cursor.p, zero4, 48, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->cursor.p, ctl_reset, sizeof(ctl_reset), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipEventRecord(a, e->stream));
     if (e->ds_on) {
       if (int rc = launch_round_ds(e, g, end, e->stream, which)) return rc;

@@ -32,6 +32,7 @@
 #include "groups_dev.h"
 #include "kernels.h"
 #include "numa_dev.h"
+#include "round_ctl.h"
 
 namespace kg {
 
@@ -984,7 +985,7 @@ __device__ __forceinline__ bool rsv_reserve(const DevTable& T, RsvNode* __restri
 // ElasticQuota: pod j's PreFilter must see the Reserve of every earlier pod.  The quota rows hold the charges of
 // pods < j - 1 (pod j - 2 was charged by rsv_select(j - 1)); pod j - 1's charge is added here explicitly when it was
 // placed (g > 0; a group's last pod is charged by rsv_apply itself), and written into the rows by rsv_select(j), when
-// no pass reads them (ws[0] = j tags it).
+// no pass reads them (ws[WS_QUOTA_TAG] = j tags it).
 // F = RSV_F_* bits, compile-time: kernels without the plugins the profile lacks need fewer registers
 constexpr int RSV_F_XF = 1, RSV_F_NUMA = 2, RSV_F_DS = 4;  // XF: X.dsx or X.rcpu set (see rsv_eval_node)
 template <int F>
@@ -998,8 +999,8 @@ __global__ __launch_bounds__(kRsvThreads) void rsv_eval(DevTable T, RsvNode* __r
                                                         unsigned long long* __restrict__ ws) {
   __shared__ uint64_t s_red[kRsvThreads / kWave];
   __shared__ int s_admit;
-  if (end < 0) end = (int64_t)ws[4];  // graph launches: the call's end lives in the workspace
-  const int64_t j = (int64_t)ws[3] + g;
+  if (end < 0) end = (int64_t)ws[WS_END];  // graph launches: the call's end lives in the workspace
+  const int64_t j = (int64_t)ws[WS_CURSOR] + g;
   if (j - 1 >= end || (g == 0 && j >= end)) return;  // uniform across the grid
   const int nb = gridDim.x;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1017,7 +1018,7 @@ __global__ __launch_bounds__(kRsvThreads) void rsv_eval(DevTable T, RsvNode* __r
       out_slot[j - 1] = slot;
       if (placed && X.nq > 0 && pods[j - 1].quota >= 0) {
         if (j >= end) rsv_quota_charge(X, pods[j - 1], j - 1);  // no later pass charges it
-        else ws[0] = (unsigned long long)j;                     // rsv_select(j) charges it
+        else ws[WS_QUOTA_TAG] = (unsigned long long)j;                     // rsv_select(j) charges it
       }
     }
     if (j >= end) return;
@@ -1170,7 +1171,7 @@ __device__ __forceinline__ int64_t rsv_total(uint64_t v, uint32_t v2, bool is_pr
 }
 
 // Pass 2: PreScore preferred node (1000), DefaultNormalizeScore of both plugins over the feasible nodes, × weights,
-// packed key; part[2 nb + b] = the block's max key.  Block 0 also charges pod j - 1's quota (tagged ws[0] = j).
+// packed key; part[2 nb + b] = the block's max key.  Block 0 also charges pod j - 1's quota (tagged ws[WS_QUOTA_TAG] = j).
 // (ABI 12) Group profiles: this pass computes PodTopologySpread's raw Score per node (its weights need the filtered
 // count and zones) with its extremes — part[13 nb + b] / part[14 nb + b] — and rsv_select2 makes the keys.
 __device__ __forceinline__ uint64_t select_key(const uint64_t* __restrict__ val, int64_t i, int64_t n, int nb,
@@ -1216,11 +1217,11 @@ __global__ __launch_bounds__(kRsvThreads) void rsv_select(const uint64_t* __rest
                                                           uint64_t* __restrict__ part,
                                                           unsigned long long* __restrict__ ws) {
   __shared__ uint64_t s_red[kRsvThreads / kWave];
-  if (end < 0) end = (int64_t)ws[4];
-  const int64_t j = (int64_t)ws[3] + g;
+  if (end < 0) end = (int64_t)ws[WS_END];
+  const int64_t j = (int64_t)ws[WS_CURSOR] + g;
   if (j >= end) return;
   const int nb = gridDim.x;
-  if (blockIdx.x == 0 && threadIdx.x == 0 && X.nq > 0 && g > 0 && ws[0] == (unsigned long long)j)
+  if (blockIdx.x == 0 && threadIdx.x == 0 && X.nq > 0 && g > 0 && ws[WS_QUOTA_TAG] == (unsigned long long)j)
     rsv_quota_charge(X, pods[j - 1], j - 1);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (!X.gpods) {
@@ -1273,8 +1274,8 @@ __global__ __launch_bounds__(kRsvThreads) void rsv_select2(const uint64_t* __res
                                                            int g, RsvParams RP, RsvExt X, uint64_t* __restrict__ part,
                                                            const unsigned long long* __restrict__ ws) {
   __shared__ uint64_t s_red[kRsvThreads / kWave];
-  if (end < 0) end = (int64_t)ws[4];
-  const int64_t j = (int64_t)ws[3] + g;
+  if (end < 0) end = (int64_t)ws[WS_END];
+  const int64_t j = (int64_t)ws[WS_CURSOR] + g;
   if (j >= end) return;
   const int nb = gridDim.x;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1296,8 +1297,8 @@ __global__ __launch_bounds__(kRsvThreads) void group_pre(DevTable T, RsvNode* __
                                                          int32_t* __restrict__ out_slot,
                                                          unsigned long long* __restrict__ ws) {
   __shared__ uint64_t s_red[kRsvThreads / kWave];
-  if (end < 0) end = (int64_t)ws[4];
-  const int64_t j = (int64_t)ws[3] + g;
+  if (end < 0) end = (int64_t)ws[WS_END];
+  const int64_t j = (int64_t)ws[WS_CURSOR] + g;
   if (j - 1 >= end || (g == 0 && j >= end)) return;  // uniform across the grid
   const int nb = gridDim.x;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1315,7 +1316,7 @@ __global__ __launch_bounds__(kRsvThreads) void group_pre(DevTable T, RsvNode* __
       out_slot[j - 1] = slot;
       if (placed && X.nq > 0 && pods[j - 1].quota >= 0) {
         if (j >= end) rsv_quota_charge(X, pods[j - 1], j - 1);
-        else ws[0] = (unsigned long long)j;
+        else ws[WS_QUOTA_TAG] = (unsigned long long)j;
       }
     }
     if (j >= end) return;
@@ -1385,8 +1386,8 @@ __global__ __launch_bounds__(kWave) void rsv_apply(DevTable T, RsvNode* __restri
                                                    const uint64_t* __restrict__ part,
                                                    uint64_t* __restrict__ out_keys, int32_t* __restrict__ out_slot,
                                                    unsigned long long* __restrict__ ws) {
-  if (end < 0) end = (int64_t)ws[4];
-  const int64_t base = (int64_t)ws[3];
+  if (end < 0) end = (int64_t)ws[WS_END];
+  const int64_t base = (int64_t)ws[WS_CURSOR];
   const int64_t j = base + g_last;
   if (base >= end) return;
   const uint64_t k = j < end ? rsv_partials_max(part + 2 * nb, nb) : 0;
@@ -1403,7 +1404,7 @@ __global__ __launch_bounds__(kWave) void rsv_apply(DevTable T, RsvNode* __restri
     out_slot[j] = slot;
     if (placed) rsv_quota_charge(X, pods[j], j);
   }
-  ws[3] = (unsigned long long)(base + g_last + 1);
+  ws[WS_CURSOR] = (unsigned long long)(base + g_last + 1);
 }
 
 __global__ void scatter_rsv(RsvNode* __restrict__ RN, int32_t* __restrict__ rsv_n, uint64_t* __restrict__ pred,

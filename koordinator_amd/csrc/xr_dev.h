@@ -2,7 +2,7 @@
 // NodeNUMAResource + DeviceShare profile, the upstream defaults): kXrPods FIFO pods per round instead of one pod per
 // device pass.  Included by engine.hip inside its kernel namespace (uses kTile / kNPT / kR / select_write).
 //
-// A round over pods [c, c + nb), c = the device cursor ws[3]:
+// A round over pods [c, c + nb), c = the device cursor ws[WS_CURSOR]:
 //   xr_eval    every (pod, node) of the round through rsv_eval_node on the round-start state (BeforePreFilter restore,
 //              every Filter, the un-normalised totals and raw Scores): val[k][i] (rsv_pack), val2[k][i] (raw
 //              TaintToleration / NodeAffinity), aff[k][i] (the NUMA affinity Reserve needs), and per (pod, tile) the
@@ -33,8 +33,8 @@ constexpr int XF_NUMA = 1, XF_DS = 2, XF_DEF = 4;
 static_assert(kXrPods < kWave, "resolver lanes");
 
 __device__ __forceinline__ bool xr_range(const unsigned long long* __restrict__ ws, int64_t& first, int& nb) {
-  first = (int64_t)ws[3];
-  const int64_t left = (int64_t)ws[4] - first;
+  first = (int64_t)ws[WS_CURSOR];
+  const int64_t left = (int64_t)ws[WS_END] - first;
   nb = left < kXrPods ? (int)left : kXrPods;
   return nb > 0;
 }
@@ -621,8 +621,8 @@ __global__ __launch_bounds__(kWave) void xr_resolve(DevTable T, RsvNode* __restr
   KG_POD_DIAG(consumed, 0u);
   __threadfence();
   if (lane == 0) {
-    ws[3] = (unsigned long long)(first + consumed);
-    ws[5] += 1;
-    ws[6] += (unsigned long long)consumed;
+    ws[WS_CURSOR] = (unsigned long long)(first + consumed);
+    ws[WS_ROUNDS] += 1;
+    ws[WS_CONSUMED] += (unsigned long long)consumed;
   }
 }
