@@ -41,6 +41,9 @@
  *   kg_pods_preempt         PostFilter's DryRunPreemption + SelectCandidate in one call: SelectVictimsOnNode for every
  *                           candidate, then upstream's pickOneNodeForPreemption reduced on the device; one node and its
  *                           victims come back.  kg_pods_pick_candidate: the pick alone, over results the caller holds.
+ *   kg_node_bound_pods_set  the bound pods preemption reads (NodeInfo.Pods), resident per node on the device;
+ *                           kg_pods_preempt_resident runs the victim selection, the PDB split, the dry run and the pick
+ *                           over that table: one pod record and a PDB budget vector go up per PostFilter call.
  *   kg_last_error           error text for the last failing call on this thread (maps to framework.NewStatus(Error,…)).
  *
  * Units follow the reference's getResourceValue (load_aware/helper.go:146-151): cpu-like resources in
@@ -958,6 +961,72 @@ int kg_pods_preempt(kg_engine* e, const kg_pod* pod, int64_t n_candidates, const
                     const int32_t* victim_minors, const uint8_t* pdb_violating, const int32_t* victim_priority,
                     const int64_t* victim_start_unix_nano, kg_preempt_pick* out_pick, int32_t* out_victims,
                     int64_t victims_cap, int32_t* out_reject /* nullable: n_candidates words */);
+
+/* (added within ABI 18: four functions, no new struct; the ABI number is unchanged)
+ * The bound pods preemption reads, resident on the device, and SelectVictimsOnNode's per-node front half run there:
+ * a PostFilter call uploads one pod record and a PDB budget vector instead of every node's victim records.
+ *   - kg_node_bound_pods_set is an informer delta like kg_node_pods_metric_set: it REPLACES the bound-pod list of each
+ *     of the n_lists nodes node_idx[l] with pods[offsets[l] .. offsets[l+1]) (an empty segment clears the list; a node
+ *     may be named once per call).  The table is the caller's NodeInfo.Pods, fed from the assigned-pod informer; its
+ *     pods are already counted in the node state (kg_pods_add), as the victims of kg_pods_select_victims are.  The
+ *     engine does not add the pods it places itself: it holds neither their priority nor their start time.
+ *       pods / slot / minors   as the victims / victim_slot / victim_minors of kg_pods_select_victims, same checks;
+ *       priority               PodPriority;         start_unix_nano   GetPodStartTime;
+ *       pdb_mask               bit b: the pod matches PDB b of the caller's dense PDB table (namespace and selector)
+ *                              and is not in that PDB's DisruptedPods (NULL = no pod matches any);
+ *       kg_pod.flags & KG_POD_NON_PREEMPTIBLE, kg_pod.quota_id and kg_pod.uid are kept with each entry.
+ *     Each list is stored in MoreImportantPod order (k8s.io/kubernetes pkg/scheduler/util, restated as published and
+ *     not pinned by a reference table): priority descending, then the earlier start first; ties keep the caller's
+ *     order (a stable sort at set time — upstream's sort.Slice is unstable there, so this is the library's rule).
+ *     Replacing a list costs host work and one copy proportional to that list, not to the table.  kg_nodes_delete
+ *     drops the lists of the deleted slots.  No scheduling kernel reads the table.
+ *   - kg_nodes_read_bound_pods reads node_idx's list back from the DEVICE copy, in stored order: out_uid[k] and
+ *     out_index[k] (the entry's index in the caller's list), at most cap of them; *out_len = its length, *out_live =
+ *     the entries of all lists; out_counters (nullable, 3 words): slab entries in use, lists moved to the slab's end
+ *     because they outgrew their place, compactions of the slab.
+ *   - kg_pods_select_victims_resident / kg_pods_preempt_resident: per candidate node, on the device, the potential
+ *     victims are the entries of its list that pass the rule — flags & KG_PREEMPT_RULE_QUOTA: Koordinator's canPreempt
+ *     (elasticquota/preempt.go:283-294: the victim is not non-preemptible, its priority is below pod_priority and its
+ *     quota_id equals pod->quota_id); without it upstream's (priority below pod_priority) — in stored order; then
+ *     filterPodsWithPDBViolation (:222-267) from a fresh copy of pdb_allowed[0 .. n_pdbs) per node: each potential
+ *     victim decrements every PDB it matches and is violating when one of them drops below 0; the reprieve order is
+ *     the violating ones, then the others, each group in stored order.  kg_pods_select_victims' kernel then runs
+ *     over those lists unchanged and, for kg_pods_preempt_resident, kg_pods_preempt's pick (rule and tie-break above).
+ *     node_idx == NULL: the candidates are the node slots 0 .. n_candidates-1, so the pick's tie-break on the lowest
+ *     position is the lowest node.  Profiles and refusals are those of kg_pods_preempt.
+ *       kg_pods_preempt_resident        out_pick, and the winner's victims in Victims.Pods order as
+ *                                       out_victim_uid[k] / out_victim_index[k] (index in the caller's list of
+ *                                       out_pick->node_idx), k < out_pick->n_victims; victims_cap below the longest
+ *                                       resident list among the candidates is KG_E_INVALID, decided before any launch;
+ *                                       out_reject (nullable): the n_candidates status words.
+ *       kg_pods_select_victims_resident the unfused form: per candidate out_reject / out_violating (as
+ *                                       kg_pods_select_victims) and out_potential (its potential victims); per
+ *                                       resident entry of the candidates, in candidate order and then the caller's list
+ *                                       order, out_entry_flags (bit 0 potential victim, bit 1 PDB-violating, bit 2
+ *                                       kept as victim) and out_entry_rank (its rank in reprieve order, -1 = not a
+ *                                       potential victim).  entries_cap = the room of the two per-entry arrays;
+ *                                       below the candidates' resident entries is KG_E_INVALID.
+ *     n_pdbs > KG_MAX_PDBS, a negative budget, or a pdb_mask bit at or above n_pdbs in a candidate's list is
+ *     KG_E_INVALID (the message names the node).  n_candidates == 0 or an empty table: candidate = -1.
+ *   - No state change: the calls use device scratch of their own; the table changes only through
+ *     kg_node_bound_pods_set and kg_nodes_delete. */
+#define KG_MAX_PDBS 64
+enum { KG_PREEMPT_RULE_QUOTA = 1 << 0 };
+int kg_node_bound_pods_set(kg_engine* e, int64_t n_lists, const int32_t* node_idx, const int64_t* offsets /* n_lists+1 */,
+                           const kg_pod* pods, const int32_t* priority, const int64_t* start_unix_nano,
+                           const int32_t* slot /* nullable */, const int32_t* minors /* nullable */,
+                           const uint64_t* pdb_mask /* nullable */);
+int kg_nodes_read_bound_pods(kg_engine* e, int32_t node_idx, int64_t* out_uid, int32_t* out_index, int64_t cap,
+                             int64_t* out_len, int64_t* out_live, int64_t* out_counters /* nullable: 3 words */);
+int kg_pods_select_victims_resident(kg_engine* e, const kg_pod* pod, int32_t pod_priority, int32_t flags,
+                                    int64_t n_candidates, const int32_t* node_idx /* nullable */,
+                                    const int32_t* pdb_allowed, int32_t n_pdbs, int32_t* out_reject,
+                                    int32_t* out_violating, int32_t* out_potential, uint8_t* out_entry_flags,
+                                    int32_t* out_entry_rank, int64_t entries_cap);
+int kg_pods_preempt_resident(kg_engine* e, const kg_pod* pod, int32_t pod_priority, int32_t flags, int64_t n_candidates,
+                             const int32_t* node_idx /* nullable */, const int32_t* pdb_allowed, int32_t n_pdbs,
+                             kg_preempt_pick* out_pick, int64_t* out_victim_uid, int32_t* out_victim_index,
+                             int64_t victims_cap, int32_t* out_reject /* nullable: n_candidates words */);
 
 const char* kg_last_error(void);
 int kg_abi_version(void);

@@ -230,6 +230,11 @@ PREEMPT_PICK_DTYPE = np.dtype([_i64("candidate"), _i64("node_idx"), _i64("eligib
                                _i64("num_violating"), _i64("first_priority"), _i64("sum_priorities"),
                                _i64("earliest_start_unix_nano")])
 
+# (added within ABI 18) the resident bound-pod table: kg_pods_select_victims_resident / kg_pods_preempt_resident
+MAX_PDBS = 64  # KG_MAX_PDBS
+PREEMPT_RULE_QUOTA = 1  # KG_PREEMPT_RULE_QUOTA: Koordinator's canPreempt (else upstream's: lower priority only)
+ENTRY_POTENTIAL, ENTRY_VIOLATING, ENTRY_VICTIM = 1, 2, 4  # bits of select_victims_resident's per-entry byte
+
 STRUCT_DTYPES = {0: CONFIG_DTYPE, 1: NODE_DTYPE, 2: METRIC_DTYPE, 3: POD_DTYPE, 4: STATS_DTYPE, 5: NODE_NUMA_DTYPE,
                  6: NODE_DEVICE_DTYPE, 7: QUOTA_DTYPE, 8: NODE_RSV_DTYPE, 9: POD_METRIC_DTYPE, 10: NODE_PRED_DTYPE,
                  11: TOPN_ROW_DTYPE, 12: FIT_DIAG_DTYPE, 13: PREEMPT_PICK_DTYPE}
@@ -252,6 +257,8 @@ EXPORTED_SYMBOLS = (
     "kg_node_pods_metric_set", "kg_debug_numa_merge", "kg_pods_evaluate_reservation", "kg_nodes_predicates_upsert",
     "kg_engine_create_hosted", "kg_pods_filter_preemption", "kg_nodes_read_pod_groups",
     "kg_pods_select_victims", "kg_debug_topn", "kg_pods_diagnose", "kg_pods_pick_candidate", "kg_pods_preempt",
+    "kg_node_bound_pods_set", "kg_nodes_read_bound_pods", "kg_pods_select_victims_resident",
+    "kg_pods_preempt_resident",
 )
 
 # int (*kg_exchange_fn)(void* user, const void* send, void* recv, int64_t bytes)
@@ -261,6 +268,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KOORDGPU_LIB") or os.path.join(PKG_DIR, "libkoordgpu.so")
 
 _lib = None
+# Symbols a library may lack without failing the load.  Empty: a missing symbol is an error.  Only an A/B timing tool
+# that drives a library built from an older commit through this binding names the entry points added since.
+OPTIONAL_SYMBOLS = ()
 
 
 class _ArrayPtr(ctypes.c_void_p):
@@ -350,9 +360,15 @@ def load_library(path: str | None = None):
         "kg_pods_diagnose": (i, [vp, vp, i64, vp, vp]),
         "kg_pods_pick_candidate": (i, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
         "kg_pods_preempt": (i, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+        "kg_node_bound_pods_set": (i, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kg_nodes_read_bound_pods": (i, [vp, i32, vp, vp, i64, vp, vp, vp]),
+        "kg_pods_select_victims_resident": (i, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, i64]),
+        "kg_pods_preempt_resident": (i, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, vp, i64, vp]),
         "kg_engine_create_hosted": (i, [vp, i64, i, i, EXCHANGE_FN, vp, ctypes.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
+        if name in OPTIONAL_SYMBOLS and not hasattr(lib, name):
+            continue
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args

@@ -3356,6 +3356,7 @@ __global__ void select_victims(DevTable T, const RsvNode* __restrict__ RN, const
 #include "topn_dev.h"
 #include "diag_dev.h"
 #include "pick_dev.h"
+#include "victims_dev.h"
 
 template <typename Rec>
 __global__ void scatter_rows(Rec* __restrict__ dst, const Rec* __restrict__ src, const int32_t* __restrict__ idx,
@@ -3821,6 +3822,30 @@ struct kg_engine {
   DevBuf<uint64_t> diag_buf;   // kg_pods_diagnose's own scratch: the pods, a chunk's partials and status words, the results
   DevBuf<int64_t> pick_buf;    // kg_pods_pick_candidate's / kg_pods_preempt's own scratch: the call's arrays, keys, partials, the pick
   DevBuf<int32_t> scratch32;
+  // the resident bound-pod table (kg_node_bound_pods_set; victims_dev.h): the host mirror in stored order, the slab
+  // and the node directory on the device, and the resident calls' own scratch
+  struct BpEntry {
+    Victim v;
+    int64_t start, quota, uid;
+    uint64_t mask;
+    int32_t prio, flags, cidx;
+  };
+  struct BpNode {
+    std::vector<BpEntry> list;
+    int64_t off = 0;
+    int32_t cap = 0;
+  };
+  std::vector<BpNode> bp;           // [capacity] once the table is used
+  std::vector<int32_t> bp_len;      // [capacity] flat copies the resident calls' checks walk
+  std::vector<uint64_t> bp_ormask;  // [capacity] OR of the list's pdb masks
+  std::vector<int32_t> bp_stamp;    // [capacity] the set call that last named the node
+  int32_t bp_call = 0;
+  int64_t bp_cap = 0, bp_used = 0, bp_live = 0, bp_garbage = 0;  // slab entries: reserved, handed out, in lists, abandoned
+  int64_t bp_relocations = 0, bp_compactions = 0;
+  std::vector<int64_t> bp_host;     // staging of one set call
+  DevBuf<int64_t> bp_slab, bp_stage;
+  DevBuf<BpDir> bp_dir;
+  DevBuf<int64_t> res_buf;     // kg_pods_select_victims_resident's / kg_pods_preempt_resident's own scratch
   std::vector<int64_t> h_static64;
   std::vector<int32_t> h_static32;
   std::vector<double> h_static_f64;
@@ -6125,6 +6150,10 @@ void kg_engine_destroy(kg_engine* e) {
   e->topn_buf.release();
   e->diag_buf.release();
   e->pick_buf.release();
+  e->bp_slab.release();
+  e->bp_stage.release();
+  e->bp_dir.release();
+  e->res_buf.release();
   e->scratch32.release();
   e->uidx.release();
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -6152,6 +6181,8 @@ int kg_nodes_upsert(kg_engine* e, const kg_node* nodes, const int32_t* idx, int6
   return 0;
 }
 
+static int bp_drop_lists(kg_engine* e, const int32_t* idx, int64_t n);
+
 int kg_nodes_delete(kg_engine* e, const int32_t* idx, int64_t n) {
   if (!e || (n > 0 && !idx)) return fail(KG_E_INVALID, "null argument");
   for (int64_t k = 0; k < n; ++k) {
@@ -6160,7 +6191,7 @@ int kg_nodes_delete(kg_engine* e, const int32_t* idx, int64_t n) {
   }
   e->static_dirty = true;
   e->np_dirty = true;
-  return 0;
+  return bp_drop_lists(e, idx, n);  // the deleted slots' bound-pod lists (no work while the table is unused)
 }
 
 static int flush_placements(kg_engine* e);
@@ -7633,6 +7664,33 @@ int kg_pods_diagnose(kg_engine* e, const kg_pod* pods, int64_t n_pods, kg_fit_di
   return 0;
 }
 
+// one victim of a dry run (an explicit list's, or an entry of the resident table), decoded and checked; k = its index
+// in the caller's array (the messages name it)
+static int decode_victim(kg_engine* e, const kg_pod& pod, int32_t s, int32_t m, int64_t k, Victim& w) {
+  DevPod v;
+  if (int rc = decode_pod(e, pod, v)) return rc;
+  if (s < -1 || s >= KG_MAX_RSV_SLOTS) return fail(KG_E_INVALID, "victim %lld: reservation slot %d", (long long)k, s);
+  if (m < 0 || m >= (1 << (8 * (1 + kXTypes)))) return fail(KG_E_INVALID, "victim %lld: minors 0x%x", (long long)k, m);
+  bool nz = false;
+  for (int q = 0; q < KG_RES_MAX; ++q) nz |= pod.requests[q] != 0;
+  // (r5) RemovePod returns before counting a reserve pod (reservation/plugin.go:286): the framework still
+  // removes it from the NodeInfo copy, but it never becomes preemptible
+  const bool reserve = (pod.flags & KG_POD_RESERVE) != 0;
+  if (reserve) nz = false;
+  w = Victim{};
+  w.req_cpu = v.req_cpu, w.req_mem = v.req_mem, w.nz_cpu = v.nz_cpu, w.nz_mem = v.nz_mem;
+  w.slot = s, w.nonzero = nz ? 1 : 0, w.reserve = reserve ? 1 : 0;
+  for (int q = 0; q < kAux; ++q) w.aux[q] = pod.requests[kAuxFirst + q];
+  w.dp.skip = 1;
+  if (e->ds_on && m != 0) {
+    if (int rc = decode_ds_pod(pod, w.dp)) return rc;
+    if (w.dp.skip || w.dp.error)
+      return fail(KG_E_INVALID, "victim %lld holds minors 0x%x but requests no valid GPU share", (long long)k, m);
+    w.dminors = m;
+  }
+  return 0;
+}
+
 // the pod and its victims of one dry-run call, decoded and checked (the shared front half of the entry points): the
 // pod through decode_lone_pod, from which PreExt — the kernels' by-value argument — is filled.
 // (r6) NodeNUMAResource, DeviceShare and TaintToleration / NodeAffinity run in the dry run too (PreExt); refused:
@@ -7655,32 +7713,10 @@ static int preempt_prepare(kg_engine* e, const kg_pod* pod, const kg_pod* victim
   if (e->ds_on) X.ds = e->ds_d.p, X.dsx = e->dsx_d.p, X.DP = e->DP;
   if (e->def_on) X.pred = e->npred.p, X.DF = e->DF;
   hv.resize((size_t)std::max<int64_t>(n_victims, 1));
-  for (int64_t k = 0; k < n_victims; ++k) {
-    DevPod v;
-    if (int rc = decode_pod(e, victims[k], v)) return rc;
-    const int32_t s = victim_slot ? victim_slot[k] : -1;
-    if (s < -1 || s >= KG_MAX_RSV_SLOTS) return fail(KG_E_INVALID, "victim %lld: reservation slot %d", (long long)k, s);
-    const int32_t m = victim_minors ? victim_minors[k] : 0;
-    if (m < 0 || m >= (1 << (8 * (1 + kXTypes)))) return fail(KG_E_INVALID, "victim %lld: minors 0x%x", (long long)k, m);
-    bool nz = false;
-    for (int q = 0; q < KG_RES_MAX; ++q) nz |= victims[k].requests[q] != 0;
-    // (r5) RemovePod returns before counting a reserve pod (reservation/plugin.go:286): the framework still
-    // removes it from the NodeInfo copy, but it never becomes preemptible
-    const bool reserve = (victims[k].flags & KG_POD_RESERVE) != 0;
-    if (reserve) nz = false;
-    Victim w{};
-    w.req_cpu = v.req_cpu, w.req_mem = v.req_mem, w.nz_cpu = v.nz_cpu, w.nz_mem = v.nz_mem;
-    w.slot = s, w.nonzero = nz ? 1 : 0, w.reserve = reserve ? 1 : 0;
-    for (int q = 0; q < kAux; ++q) w.aux[q] = victims[k].requests[kAuxFirst + q];
-    w.dp.skip = 1;
-    if (e->ds_on && m != 0) {
-      if (int rc = decode_ds_pod(victims[k], w.dp)) return rc;
-      if (w.dp.skip || w.dp.error)
-        return fail(KG_E_INVALID, "victim %lld holds minors 0x%x but requests no valid GPU share", (long long)k, m);
-      w.dminors = m;
-    }
-    hv[k] = w;
-  }
+  for (int64_t k = 0; k < n_victims; ++k)
+    if (int rc = decode_victim(e, victims[k], victim_slot ? victim_slot[k] : -1, victim_minors ? victim_minors[k] : 0, k,
+                               hv[k]))
+      return rc;
   return 0;
 }
 
@@ -7756,6 +7792,18 @@ static DryRunLayout dry_run_layout(Carver& C, int64_t n_candidates, int64_t nv, 
                       C.take<uint8_t>(nvs),    C.take<int32_t>(nc)};
 }
 
+// select_victims over one call's arrays in `b`, on the engine stream
+static int dry_run_kernel(kg_engine* e, int64_t* b, const DryRunLayout& L, int64_t n_candidates, const uint8_t* gviol,
+                          const LonePod& lp, const PreExt& X) {
+  const unsigned blocks = (unsigned)((n_candidates + kWave - 1) / kWave);
+  select_victims<<<blocks, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, e->rsv_pd.p, L.sel.at(b), L.pod.at(b),
+                                                  L.aux.at(b), lp.rpod, e->P, e->RP, e->rsv_on ? 1 : 0, n_candidates,
+                                                  L.nodes.at(b), L.off.at(b), L.vic.at(b), gviol, L.rej.at(b),
+                                                  L.out.at(b), L.nvio.at(b), X);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // uploads one dry-run call into its arrays in `b` and launches select_victims over them on the engine stream; the
 // outputs stay on the device
 static int dry_run_launch(kg_engine* e, int64_t* b, const DryRunLayout& L, int64_t n_candidates, const int32_t* node_idx,
@@ -7772,13 +7820,7 @@ static int dry_run_launch(kg_engine* e, int64_t* b, const DryRunLayout& L, int64
     HIP_TRY(hipMemcpyAsync(L.viol.at(b), pdb_violating, (size_t)nv, hipMemcpyHostToDevice, e->stream));
     gviol = L.viol.at(b);
   }
-  const unsigned blocks = (unsigned)((n_candidates + kWave - 1) / kWave);
-  select_victims<<<blocks, kWave, 0, e->stream>>>(e->T, e->rsv_d.p, e->rsv_nd.p, e->rsv_pd.p, L.sel.at(b), L.pod.at(b),
-                                                  L.aux.at(b), lp.rpod, e->P, e->RP, e->rsv_on ? 1 : 0, n_candidates,
-                                                  L.nodes.at(b), L.off.at(b), L.vic.at(b), gviol, L.rej.at(b),
-                                                  L.out.at(b), L.nvio.at(b), X);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return dry_run_kernel(e, b, L, n_candidates, gviol, lp, X);
 }
 
 int kg_pods_select_victims(kg_engine* e, const kg_pod* pod, int64_t n_candidates, const int32_t* node_idx,
@@ -7832,8 +7874,8 @@ static PickTail pick_tail(Carver& C, int64_t n_candidates, int64_t max_seg) {
   return PickTail{C.take<PickKey>((size_t)n_candidates), C.take<PickPart>(kPickBlocks), C.take<kg_preempt_pick>(1),
                   C.take<int32_t>((size_t)max_seg)};
 }
-static int pick_run(kg_engine* e, int64_t n_candidates, int64_t max_seg, const PickDev& D, const PickTail& t, int64_t* b,
-                    kg_preempt_pick* out_pick, int32_t* out_victims) {
+static int pick_launch(kg_engine* e, int64_t n_candidates, int64_t max_seg, const PickDev& D, const PickTail& t,
+                       int64_t* b) {
   const int64_t nb = (n_candidates + kPickWaves - 1) / kPickWaves;
   const int np = (int)std::min<int64_t>((n_candidates + kPickThreads - 1) / kPickThreads, kPickBlocks);
   pick_keys<<<(unsigned)nb, kPickThreads, 0, e->stream>>>(n_candidates, D.off, D.rej, D.kept, D.nvio, D.prio, D.start,
@@ -7841,6 +7883,11 @@ static int pick_run(kg_engine* e, int64_t n_candidates, int64_t max_seg, const P
   pick_reduce<<<(unsigned)np, kPickThreads, 0, e->stream>>>(t.key.at(b), n_candidates, t.part.at(b));
   pick_final<<<1, kPickThreads, 0, e->stream>>>(t.part.at(b), np, D.nodes, D.off, D.kept, t.hdr.at(b), t.vic.at(b), max_seg);
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+static int pick_run(kg_engine* e, int64_t n_candidates, int64_t max_seg, const PickDev& D, const PickTail& t, int64_t* b,
+                    kg_preempt_pick* out_pick, int32_t* out_victims) {
+  if (int rc = pick_launch(e, n_candidates, max_seg, D, t, b)) return rc;
   std::vector<int64_t> host(t.hdr.words() + t.vic.words());
   HIP_TRY(hipMemcpyAsync(host.data(), t.hdr.at(b), host.size() * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -7945,6 +7992,408 @@ int kg_pods_preempt(kg_engine* e, const kg_pod* pod, int64_t n_candidates, const
     HIP_TRY(hipMemcpyAsync(out_reject, L.rej.at(b), (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
   const PickDev D{L.nodes.at(b), L.off.at(b), L.rej.at(b), L.out.at(b), L.nvio.at(b), s_prio.at(b), s_start.at(b)};
   return pick_run(e, n_candidates, max_seg, D, t, b, out_pick, out_victims);
+}
+
+// ---- the resident bound-pod table (added within ABI 18; victims_dev.h) ----
+
+constexpr int64_t kBpMinSlab = 1024;    // slab entries reserved at least
+constexpr int64_t kBpMinGarbage = 256;  // abandoned entries below which the slab is not compacted
+
+// the arrays of BpCols for n entries, in a buffer of 8-byte words (the slab, or a set call's staging)
+struct BpSlots {
+  Slot<Victim> vic;
+  Slot<int32_t> prio;
+  Slot<int64_t> start;
+  Slot<int32_t> flags;
+  Slot<int64_t> quota;
+  Slot<uint64_t> mask;
+  Slot<int64_t> uid;
+  Slot<int32_t> cidx;
+};
+static BpSlots bp_carve(Carver& C, int64_t n) {
+  const size_t k = (size_t)std::max<int64_t>(n, 1);
+  return BpSlots{C.take<Victim>(k),  C.take<int32_t>(k),  C.take<int64_t>(k), C.take<int32_t>(k),
+                 C.take<int64_t>(k), C.take<uint64_t>(k), C.take<int64_t>(k), C.take<int32_t>(k)};
+}
+static BpCols bp_cols(const BpSlots& s, int64_t* b) {
+  return BpCols{s.vic.at(b), s.prio.at(b), s.start.at(b), s.flags.at(b), s.quota.at(b), s.mask.at(b), s.uid.at(b), s.cidx.at(b)};
+}
+static BpCols bp_slab_cols(kg_engine* e) {
+  Carver C;
+  return bp_cols(bp_carve(C, e->bp_cap), e->bp_slab.p);
+}
+
+// the host mirror, the directory (zeroed: every list empty) and a first slab, once the table is used
+static int bp_ready(kg_engine* e) {
+  if (!e->bp.empty()) return 0;
+  const size_t cap = (size_t)std::max<int64_t>(e->capacity, 1);
+  if (int rc = e->bp_dir.ensure(cap)) return rc;
+  HIP_TRY(hipMemsetAsync(e->bp_dir.p, 0, cap * sizeof(BpDir), e->stream));
+  Carver C;
+  bp_carve(C, kBpMinSlab);
+  if (int rc = e->bp_slab.ensure(C.words())) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->bp_cap = kBpMinSlab;
+  e->bp.resize(cap);
+  e->bp_len.assign(cap, 0);
+  e->bp_ormask.assign(cap, 0);
+  e->bp_stamp.assign(cap, 0);
+  return 0;
+}
+
+// writes the mirror's lists of `nodes` (placed: off / cap final, inside the slab) to the device: one staging copy, one
+// scatter launch
+static int bp_upload(kg_engine* e, const std::vector<int32_t>& nodes) {
+  if (nodes.empty()) return 0;
+  int64_t total = 0;
+  for (int32_t i : nodes) total += (int64_t)e->bp[i].list.size();
+  Carver C;
+  const BpSlots S = bp_carve(C, total);
+  const auto s_lists = C.take<BpList>(nodes.size());
+  e->bp_host.assign(C.words(), 0);
+  int64_t* h = e->bp_host.data();
+  const BpCols H = bp_cols(S, h);
+  BpList* hl = s_lists.at(h);
+  int64_t at = 0;
+  for (size_t l = 0; l < nodes.size(); ++l) {
+    const kg_engine::BpNode& N = e->bp[nodes[l]];
+    hl[l] = BpList{N.off, at, nodes[l], (int32_t)N.list.size(), N.cap, 0};
+    for (const kg_engine::BpEntry& q : N.list) {
+      H.vic[at] = q.v, H.prio[at] = q.prio, H.start[at] = q.start, H.flags[at] = q.flags, H.quota[at] = q.quota;
+      H.mask[at] = q.mask, H.uid[at] = q.uid, H.cidx[at] = q.cidx;
+      ++at;
+    }
+  }
+  if (int rc = e->bp_stage.ensure(C.words())) return rc;
+  int64_t* b = e->bp_stage.p;
+  HIP_TRY(hipMemcpyAsync(b, h, C.words() * 8, hipMemcpyHostToDevice, e->stream));
+  const unsigned blocks = (unsigned)((nodes.size() + kRvWaves - 1) / kRvWaves);
+  bp_scatter<<<blocks, kRvThreads, 0, e->stream>>>((int64_t)nodes.size(), s_lists.at(b), bp_cols(S, b), bp_slab_cols(e),
+                                                   e->bp_dir.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));  // the staging vector is reused by the next call
+  return 0;
+}
+
+// lays every list out again from the mirror, back to back (cap = len), in a slab of twice the live size
+static int bp_rebuild(kg_engine* e) {
+  std::vector<int32_t> nodes;
+  int64_t at = 0;
+  for (size_t i = 0; i < e->bp.size(); ++i) {
+    kg_engine::BpNode& N = e->bp[i];
+    N.off = at, N.cap = (int32_t)N.list.size();
+    at += N.cap;
+    if (N.cap) nodes.push_back((int32_t)i);
+  }
+  e->bp_used = at, e->bp_garbage = 0;
+  const int64_t want = std::max<int64_t>(2 * at, kBpMinSlab);
+  Carver C;
+  bp_carve(C, want);
+  if (int rc = e->bp_slab.ensure(C.words())) return rc;
+  e->bp_cap = want;
+  HIP_TRY(hipMemsetAsync(e->bp_dir.p, 0, e->bp.size() * sizeof(BpDir), e->stream));
+  return bp_upload(e, nodes);
+}
+
+// the mirror's lists of `nodes` were replaced (lists[l] in stored order): place them and write them to the device.
+// A list that fits its place is overwritten there, a longer one goes to the slab's end; the slab is laid out again
+// when it is full or its abandoned places outweigh the live entries.
+static int bp_replace(kg_engine* e, const std::vector<int32_t>& nodes, std::vector<std::vector<kg_engine::BpEntry>>& lists) {
+  for (size_t l = 0; l < nodes.size(); ++l) {
+    kg_engine::BpNode& N = e->bp[nodes[l]];
+    const int64_t len = (int64_t)lists[l].size();
+    e->bp_live += len - (int64_t)N.list.size();
+    if (len > N.cap) {
+      if (N.cap > 0) ++e->bp_relocations;
+      e->bp_garbage += N.cap;
+      N.off = e->bp_used, N.cap = (int32_t)len;
+      e->bp_used += len;
+    }
+    uint64_t om = 0;
+    for (const kg_engine::BpEntry& q : lists[l]) om |= q.mask;
+    N.list = std::move(lists[l]);
+    e->bp_len[nodes[l]] = (int32_t)len;
+    e->bp_ormask[nodes[l]] = om;
+  }
+  if (e->bp_used > e->bp_cap || (e->bp_garbage >= kBpMinGarbage && e->bp_garbage > e->bp_live)) {
+    if (e->bp_garbage > 0) ++e->bp_compactions;  // abandoned places are reclaimed (else the slab only grows)
+    return bp_rebuild(e);
+  }
+  return bp_upload(e, nodes);
+}
+
+static int bp_drop_lists(kg_engine* e, const int32_t* idx, int64_t n) {
+  if (e->bp.empty()) return 0;
+  std::vector<int32_t> nodes;
+  for (int64_t k = 0; k < n; ++k)
+    if (e->bp_len[idx[k]] > 0 && std::find(nodes.begin(), nodes.end(), idx[k]) == nodes.end()) nodes.push_back(idx[k]);
+  if (nodes.empty()) return 0;
+  std::vector<std::vector<kg_engine::BpEntry>> lists(nodes.size());
+  return bp_replace(e, nodes, lists);
+}
+
+int kg_node_bound_pods_set(kg_engine* e, int64_t n_lists, const int32_t* node_idx, const int64_t* offsets,
+                           const kg_pod* pods, const int32_t* priority, const int64_t* start_unix_nano,
+                           const int32_t* slot, const int32_t* minors, const uint64_t* pdb_mask) {
+  if (!e || n_lists < 0 || (n_lists > 0 && (!node_idx || !offsets))) return fail(KG_E_INVALID, "null argument");
+  if (n_lists == 0) return 0;
+  if (offsets[0] != 0) return fail(KG_E_INVALID, "offsets[0] must be 0");
+  const int64_t total = offsets[n_lists];
+  if (total < 0 || total > INT32_MAX) return fail(KG_E_INVALID, "kg_node_bound_pods_set: %lld pods", (long long)total);
+  if (total > 0 && (!pods || !priority || !start_unix_nano)) return fail(KG_E_INVALID, "null argument");
+  if (int rc = bp_ready(e)) return rc;
+  // every list is checked and decoded before the mirror or the device changes: a refused call leaves the table as it was
+  ++e->bp_call;
+  std::vector<int32_t> nodes((size_t)n_lists);
+  std::vector<std::vector<kg_engine::BpEntry>> lists((size_t)n_lists);
+  std::vector<int32_t> order;
+  int64_t grow = 0;
+  for (int64_t l = 0; l < n_lists; ++l) {
+    const int32_t i = node_idx[l];
+    if (i < 0 || i >= e->n_nodes)
+      return fail(KG_E_INVALID, "list %lld: node index %d outside [0, %lld)", (long long)l, i, (long long)e->n_nodes);
+    if (e->bp_stamp[i] == e->bp_call) return fail(KG_E_INVALID, "list %lld: node %d is named twice in one call", (long long)l, i);
+    e->bp_stamp[i] = e->bp_call;
+    const int64_t k0 = offsets[l], k1 = offsets[l + 1];
+    if (k1 < k0) return fail(KG_E_INVALID, "offsets decrease at list %lld", (long long)l);
+    nodes[l] = i;
+    grow += k1 - k0;
+    // MoreImportantPod: priority descending, then the earlier start; a stable sort keeps the caller's order on ties
+    order.resize((size_t)(k1 - k0));
+    for (int64_t k = k0; k < k1; ++k) order[k - k0] = (int32_t)(k - k0);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+      if (priority[k0 + a] != priority[k0 + b]) return priority[k0 + a] > priority[k0 + b];
+      return start_unix_nano[k0 + a] < start_unix_nano[k0 + b];
+    });
+    lists[l].resize(order.size());
+    for (size_t r = 0; r < order.size(); ++r) {
+      const int64_t k = k0 + order[r];
+      kg_engine::BpEntry& q = lists[l][r];
+      if (int rc = decode_victim(e, pods[k], slot ? slot[k] : -1, minors ? minors[k] : 0, k, q.v)) return rc;
+      q.prio = priority[k], q.start = start_unix_nano[k], q.flags = (int32_t)(pods[k].flags & KG_POD_NON_PREEMPTIBLE);
+      q.quota = pods[k].quota_id, q.uid = pods[k].uid, q.mask = pdb_mask ? pdb_mask[k] : 0, q.cidx = order[r];
+    }
+  }
+  if (e->bp_used + grow > INT32_MAX) return fail(KG_E_INVALID, "kg_node_bound_pods_set: the table would pass 2^31 entries");
+  return bp_replace(e, nodes, lists);
+}
+
+int kg_nodes_read_bound_pods(kg_engine* e, int32_t node_idx, int64_t* out_uid, int32_t* out_index, int64_t cap,
+                             int64_t* out_len, int64_t* out_live, int64_t* out_counters) {
+  if (!e || !out_len || !out_live || cap < 0 || (cap > 0 && (!out_uid || !out_index)))
+    return fail(KG_E_INVALID, "null argument");
+  if (node_idx < 0 || node_idx >= e->capacity)
+    return fail(KG_E_INVALID, "node index %d outside [0, %lld)", node_idx, (long long)e->capacity);
+  *out_len = *out_live = 0;
+  if (out_counters) out_counters[0] = e->bp_used, out_counters[1] = e->bp_relocations, out_counters[2] = e->bp_compactions;
+  if (e->bp.empty()) return 0;
+  std::vector<BpDir> dir(e->bp.size());
+  HIP_TRY(hipMemcpyAsync(dir.data(), e->bp_dir.p, dir.size() * sizeof(BpDir), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (const BpDir& d : dir) *out_live += d.len;
+  const BpDir d = dir[(size_t)node_idx];
+  if (d.len < 0 || d.off < 0 || d.off + d.len > e->bp_cap)
+    return fail(KG_E_DEVICE, "kg_nodes_read_bound_pods: node %d: directory entry (%lld, %d)", node_idx, (long long)d.off, d.len);
+  *out_len = d.len;
+  const int64_t n = std::min<int64_t>(d.len, cap);
+  if (n > 0) {
+    const BpCols B = bp_slab_cols(e);
+    HIP_TRY(hipMemcpyAsync(out_uid, B.uid + d.off, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(out_index, B.cidx + d.off, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+  }
+  return 0;
+}
+
+// one resident call's candidates and PDB budgets, checked against the host mirror before any launch.  entries = the
+// candidates' resident entries (the bound of the call's arrays), max_len = the longest list among them.
+static int resident_check(kg_engine* e, const char* who, int64_t n_candidates, const int32_t* node_idx,
+                          const int32_t* pdb_allowed, int32_t n_pdbs, int64_t& entries, int64_t& max_len) {
+  if (n_pdbs < 0 || n_pdbs > KG_MAX_PDBS) return fail(KG_E_INVALID, "%s: %d PDBs outside 0..%d", who, (int)n_pdbs, KG_MAX_PDBS);
+  if (n_pdbs > 0 && !pdb_allowed) return fail(KG_E_INVALID, "null argument");
+  for (int32_t b = 0; b < n_pdbs; ++b)
+    if (pdb_allowed[b] < 0) return fail(KG_E_INVALID, "%s: pdb_allowed[%d] = %d", who, (int)b, pdb_allowed[b]);
+  if (n_candidates > INT32_MAX) return fail(KG_E_INVALID, "%s: %lld candidates", who, (long long)n_candidates);
+  if (!node_idx && n_candidates > e->n_nodes)
+    return fail(KG_E_INVALID, "%s: %lld candidates without node indices, the table has %lld nodes", who,
+                (long long)n_candidates, (long long)e->n_nodes);
+  const uint64_t outside = n_pdbs >= 64 ? 0 : ~((1ull << n_pdbs) - 1);
+  entries = max_len = 0;
+  for (int64_t c = 0; c < n_candidates; ++c) {
+    const int64_t i = node_idx ? node_idx[c] : c;
+    if (i < 0 || i >= e->n_nodes)
+      return fail(KG_E_INVALID, "candidate %lld: node index %d outside [0, %lld)", (long long)c, (int)i, (long long)e->n_nodes);
+    if (e->bp_ormask[i] & outside)
+      return fail(KG_E_INVALID, "%s: node %d holds a pod whose pdb_mask has a bit at or above n_pdbs = %d", who, (int)i,
+                  (int)n_pdbs);
+    entries += e->bp_len[i];
+    max_len = std::max<int64_t>(max_len, e->bp_len[i]);
+  }
+  if (entries > INT32_MAX) return fail(KG_E_INVALID, "%s: %lld resident entries (positions are int32)", who, (long long)entries);
+  return 0;
+}
+
+// a resident call's device arrays behind the dry run's: the pick's per-victim inputs, where each entry came from, the
+// per-candidate counts, the budgets, and the per-slab-entry byte (and rank, for the unfused form)
+struct ResidentLayout {
+  DryRunLayout L;
+  Slot<int32_t> prio;
+  Slot<int64_t> start;
+  Slot<int32_t> src;
+  Slot<int32_t> cnt;     // [2 * n_candidates]
+  Slot<int32_t> pdb;     // [KG_MAX_PDBS]
+  Slot<int32_t> cand;    // the caller's node indices
+  Slot<uint8_t> eflag;   // [slab entries]
+  Slot<int32_t> erank;   // [slab entries], unfused only
+};
+static ResidentLayout resident_layout(kg_engine* e, Carver& C, int64_t n_candidates, int64_t entries, bool ranks) {
+  const size_t nc = (size_t)n_candidates, nvs = (size_t)std::max<int64_t>(entries, 1);
+  ResidentLayout R;
+  R.L = dry_run_layout(C, n_candidates, entries, nvs);
+  R.prio = C.take<int32_t>(nvs), R.start = C.take<int64_t>(nvs), R.src = C.take<int32_t>(nvs);
+  R.cnt = C.take<int32_t>(2 * nc), R.pdb = C.take<int32_t>(KG_MAX_PDBS), R.cand = C.take<int32_t>(nc);
+  R.eflag = C.take<uint8_t>((size_t)e->bp_cap), R.erank = C.take<int32_t>(ranks ? (size_t)e->bp_cap : 0);
+  return R;
+}
+
+// uploads the pod and the budgets, then select → scan → compact → select_victims over e->res_buf, in stream order
+static int resident_launch(kg_engine* e, int64_t* b, const ResidentLayout& R, const kg_pod* pod, int32_t pod_priority,
+                           int32_t flags, int64_t n_candidates, const int32_t* node_idx, const int32_t* pdb_allowed,
+                           int32_t n_pdbs, const LonePod& lp, const PreExt& X) {
+  const DryRunLayout& L = R.L;
+  HIP_TRY(hipMemcpyAsync(L.pod.at(b), &lp.pod, sizeof(lp.pod), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(L.aux.at(b), lp.aux, sizeof(lp.aux), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(L.sel.at(b), &lp.sel, sizeof(lp.sel), hipMemcpyHostToDevice, e->stream));
+  if (n_pdbs > 0) HIP_TRY(hipMemcpyAsync(R.pdb.at(b), pdb_allowed, (size_t)n_pdbs * 4, hipMemcpyHostToDevice, e->stream));
+  const int32_t* gcand = nullptr;
+  if (node_idx) {
+    HIP_TRY(hipMemcpyAsync(R.cand.at(b), node_idx, (size_t)n_candidates * 4, hipMemcpyHostToDevice, e->stream));
+    gcand = R.cand.at(b);
+  }
+  const RvCall call{pod->quota_id, pod_priority, (flags & KG_PREEMPT_RULE_QUOTA) ? 1 : 0, n_pdbs, 0};
+  const BpCols B = bp_slab_cols(e);
+  const unsigned blocks = (unsigned)((n_candidates + kRvWaves - 1) / kRvWaves);
+  rv_select<<<blocks, kRvThreads, 0, e->stream>>>(B, e->bp_dir.p, n_candidates, gcand, call, R.pdb.at(b), L.nodes.at(b),
+                                                  R.cnt.at(b), R.eflag.at(b));
+  rv_scan<<<1, kRvScanThreads, 0, e->stream>>>(R.cnt.at(b), n_candidates, L.off.at(b));
+  rv_compact<<<blocks, kRvThreads, 0, e->stream>>>(B, e->bp_dir.p, n_candidates, L.nodes.at(b), R.cnt.at(b), L.off.at(b),
+                                                   R.eflag.at(b), L.vic.at(b), L.viol.at(b), R.prio.at(b), R.start.at(b),
+                                                   R.src.at(b), R.erank.count ? R.erank.at(b) : nullptr);
+  HIP_TRY(hipGetLastError());
+  return dry_run_kernel(e, b, L, n_candidates, L.viol.at(b), lp, X);
+}
+
+int kg_pods_select_victims_resident(kg_engine* e, const kg_pod* pod, int32_t pod_priority, int32_t flags,
+                                    int64_t n_candidates, const int32_t* node_idx, const int32_t* pdb_allowed,
+                                    int32_t n_pdbs, int32_t* out_reject, int32_t* out_violating, int32_t* out_potential,
+                                    uint8_t* out_entry_flags, int32_t* out_entry_rank, int64_t entries_cap) {
+  if (!e || !pod || n_candidates < 0 || entries_cap < 0 ||
+      (n_candidates > 0 && (!out_reject || !out_violating || !out_potential)))
+    return fail(KG_E_INVALID, "null argument");
+  if (n_candidates == 0) return 0;
+  if (int rc = bp_ready(e)) return rc;
+  int64_t entries, max_len;
+  if (int rc = resident_check(e, "kg_pods_select_victims_resident", n_candidates, node_idx, pdb_allowed, n_pdbs, entries,
+                              max_len))
+    return rc;
+  if (entries_cap < entries)
+    return fail(KG_E_INVALID, "entries_cap %lld below the candidates' %lld resident entries", (long long)entries_cap,
+                (long long)entries);
+  if (entries > 0 && (!out_entry_flags || !out_entry_rank)) return fail(KG_E_INVALID, "null argument");
+  LonePod lp;  // lives until the stream is synchronised
+  std::vector<Victim> hv;
+  PreExt X;
+  if (int rc = preempt_prepare(e, pod, nullptr, nullptr, nullptr, 0, lp, hv, X)) return rc;
+  const size_t nc = (size_t)n_candidates, nvs = (size_t)std::max<int64_t>(entries, 1);
+  Carver C;
+  const ResidentLayout R = resident_layout(e, C, n_candidates, entries, true);
+  const auto s_ebase = C.take<int64_t>(nc);
+  const auto s_oflag = C.take<uint8_t>(nvs);
+  const auto s_orank = C.take<int32_t>(nvs);
+  if (int rc = e->res_buf.ensure(C.words())) return rc;
+  int64_t* b = e->res_buf.p;
+  std::vector<int64_t> ebase(nc);  // where each candidate's entries start in the per-entry outputs
+  int64_t at = 0;
+  for (size_t c = 0; c < nc; ++c) {
+    ebase[c] = at;
+    at += e->bp_len[node_idx ? node_idx[c] : (int32_t)c];
+  }
+  HIP_TRY(hipMemcpyAsync(s_ebase.at(b), ebase.data(), nc * 8, hipMemcpyHostToDevice, e->stream));
+  if (int rc = resident_launch(e, b, R, pod, pod_priority, flags, n_candidates, node_idx, pdb_allowed, n_pdbs, lp, X))
+    return rc;
+  const DryRunLayout& L = R.L;
+  const unsigned blocks = (unsigned)((n_candidates + kRvWaves - 1) / kRvWaves);
+  rv_export<<<blocks, kRvThreads, 0, e->stream>>>(bp_slab_cols(e), e->bp_dir.p, n_candidates, L.nodes.at(b), L.off.at(b),
+                                                  s_ebase.at(b), R.eflag.at(b), R.erank.at(b), L.out.at(b), s_oflag.at(b),
+                                                  s_orank.at(b));
+  HIP_TRY(hipGetLastError());
+  std::vector<int32_t> cnt(2 * nc);
+  HIP_TRY(hipMemcpyAsync(out_reject, L.rej.at(b), nc * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_violating, L.nvio.at(b), nc * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(cnt.data(), R.cnt.at(b), 2 * nc * 4, hipMemcpyDeviceToHost, e->stream));
+  if (entries > 0) {
+    HIP_TRY(hipMemcpyAsync(out_entry_flags, s_oflag.at(b), (size_t)entries, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(out_entry_rank, s_orank.at(b), (size_t)entries * 4, hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t c = 0; c < nc; ++c) out_potential[c] = cnt[2 * c];
+  return 0;
+}
+
+// the dry run over the resident table and the pick in one call: five launches in front of kg_pods_preempt's pick, one
+// after it, all in stream order over e->res_buf; the pick header, the winner's uids and caller indices come back in
+// one copy.  Refusals are kg_pods_preempt's, through the same preempt_prepare.
+int kg_pods_preempt_resident(kg_engine* e, const kg_pod* pod, int32_t pod_priority, int32_t flags, int64_t n_candidates,
+                             const int32_t* node_idx, const int32_t* pdb_allowed, int32_t n_pdbs,
+                             kg_preempt_pick* out_pick, int64_t* out_victim_uid, int32_t* out_victim_index,
+                             int64_t victims_cap, int32_t* out_reject) {
+  if (!e || !pod || !out_pick || n_candidates < 0 || victims_cap < 0) return fail(KG_E_INVALID, "null argument");
+  *out_pick = kPickNoCandidate;
+  if (n_candidates == 0) return 0;
+  if (int rc = bp_ready(e)) return rc;
+  int64_t entries, max_len;
+  if (int rc = resident_check(e, "kg_pods_preempt_resident", n_candidates, node_idx, pdb_allowed, n_pdbs, entries, max_len))
+    return rc;
+  if (victims_cap < max_len)
+    return fail(KG_E_INVALID, "victims_cap %lld below the longest resident list among the candidates %lld",
+                (long long)victims_cap, (long long)max_len);
+  if (max_len > 0 && (!out_victim_uid || !out_victim_index)) return fail(KG_E_INVALID, "null argument");
+  LonePod lp;  // lives until the stream is synchronised
+  std::vector<Victim> hv;
+  PreExt X;
+  if (int rc = preempt_prepare(e, pod, nullptr, nullptr, nullptr, 0, lp, hv, X)) return rc;
+  Carver C;
+  const ResidentLayout R = resident_layout(e, C, n_candidates, entries, false);
+  const PickTail t = pick_tail(C, n_candidates, max_len);  // the header, then the positions
+  const auto s_uid = C.take<int64_t>((size_t)max_len);     // then the uids and the caller indices: one copy back
+  const auto s_cidx = C.take<int32_t>((size_t)max_len);
+  if (int rc = e->res_buf.ensure(C.words())) return rc;
+  int64_t* b = e->res_buf.p;
+  if (int rc = resident_launch(e, b, R, pod, pod_priority, flags, n_candidates, node_idx, pdb_allowed, n_pdbs, lp, X))
+    return rc;
+  const DryRunLayout& L = R.L;
+  if (out_reject)
+    HIP_TRY(hipMemcpyAsync(out_reject, L.rej.at(b), (size_t)n_candidates * 4, hipMemcpyDeviceToHost, e->stream));
+  const PickDev D{L.nodes.at(b), L.off.at(b), L.rej.at(b), L.out.at(b), L.nvio.at(b), R.prio.at(b), R.start.at(b)};
+  if (int rc = pick_launch(e, n_candidates, max_len, D, t, b)) return rc;
+  rv_winner<<<1, kRvThreads, 0, e->stream>>>(t.hdr.at(b), t.vic.at(b), R.src.at(b), bp_slab_cols(e), max_len, s_uid.at(b),
+                                             s_cidx.at(b));
+  HIP_TRY(hipGetLastError());
+  std::vector<int64_t> host(t.hdr.words() + t.vic.words() + s_uid.words() + s_cidx.words());
+  HIP_TRY(hipMemcpyAsync(host.data(), t.hdr.at(b), host.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  kg_preempt_pick h;
+  std::memcpy(&h, host.data(), sizeof(h));
+  if (h.candidate < -1 || h.candidate >= n_candidates || h.n_victims < 0 || h.n_victims > max_len)
+    return fail(KG_E_DEVICE, "preemption pick: candidate %lld with %lld victims", (long long)h.candidate,
+                (long long)h.n_victims);
+  *out_pick = h;
+  if (h.n_victims > 0) {
+    const int64_t* hu = host.data() + t.hdr.words() + t.vic.words();
+    std::memcpy(out_victim_uid, hu, (size_t)h.n_victims * 8);
+    std::memcpy(out_victim_index, hu + s_uid.words(), (size_t)h.n_victims * 4);
+  }
+  return 0;
 }
 
 int kg_results_fetch_reservations(kg_engine* e, int64_t first, int64_t count, int32_t* out_slot) {

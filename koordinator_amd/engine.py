@@ -491,6 +491,95 @@ class Engine:
         victims = victims.astype(np.int32)
         return (pick[0], victims, rej[:nc]) if want_reject else (pick[0], victims)
 
+    # -- the resident bound-pod table (added within ABI 18) ------------------------------------------------
+    def set_bound_pods(self, nodes, pods_per_node, priorities_per_node, starts_per_node, slots_per_node=None,
+                       minors_per_node=None, pdb_masks_per_node=None):
+        """kg_node_bound_pods_set: replaces the bound-pod list (NodeInfo.Pods) of each node of `nodes`; an empty list
+        clears it.  pods_per_node[l]: POD_DTYPE records; priorities (PodPriority), starts (GetPodStartTime, unix
+        nanoseconds), slots / minors (as for select_victims) and pdb_masks (uint64, bit b = the pod matches PDB b and is
+        not in its DisruptedPods) per pod.  A priority outside int32 is refused with E_INVALID."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        off = np.zeros(len(nodes) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(v) for v in pods_per_node], dtype=np.int64)
+        nv = int(off[-1])
+
+        def flat(per_node, dtype):
+            if not nv:
+                return np.zeros(1, dtype=dtype)
+            # joined as bytes: numpy concatenates records field by field, ten times slower at 100k lists
+            parts = [np.ascontiguousarray(np.asarray(v, dtype=dtype).reshape(-1)).view(np.uint8) for v in per_node]
+            a = np.concatenate(parts).view(dtype)
+            if len(a) != nv:
+                raise ValueError("set_bound_pods: a per-pod list does not match its node's pods")
+            return a
+
+        pr64 = flat(priorities_per_node, np.int64)
+        if nv and (pr64.min() < -2**31 or pr64.max() > 2**31 - 1):
+            raise abi.KoordGPUError(abi.E_INVALID, "set_bound_pods: a priority outside int32")
+        pods = flat(pods_per_node, abi.POD_DTYPE)
+        pr = pr64.astype(np.int32)
+        stt = flat(starts_per_node, np.int64)
+        sl = flat(slots_per_node, np.int32) if slots_per_node is not None and nv else None
+        mi = flat(minors_per_node, np.int32) if minors_per_node is not None and nv else None
+        pm = flat(pdb_masks_per_node, np.uint64) if pdb_masks_per_node is not None and nv else None
+        check(self.lib, self.lib.kg_node_bound_pods_set(self.h, len(nodes), ptr(nodes), ptr(off), ptr(pods), ptr(pr),
+                                                        ptr(stt), ptr(sl), ptr(mi), ptr(pm)))
+
+    def read_bound_pods(self, node: int):
+        """kg_nodes_read_bound_pods: node's list from the DEVICE copy in stored (MoreImportantPod) order.  Returns (uid
+        int64[len], caller-list index int32[len], info) with info = {"live": entries of all lists, "used": slab entries
+        in use, "relocations", "compactions"}."""
+        n, live, counters = np.zeros(1, np.int64), np.zeros(1, np.int64), np.zeros(3, np.int64)
+        check(self.lib, self.lib.kg_nodes_read_bound_pods(self.h, int(node), None, None, 0, ptr(n), ptr(live), None))
+        cap = int(n[0])
+        uid, idx = np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.int32)
+        check(self.lib, self.lib.kg_nodes_read_bound_pods(self.h, int(node), ptr(uid), ptr(idx), cap, ptr(n), ptr(live),
+                                                          ptr(counters)))
+        info = {"live": int(live[0]), "used": int(counters[0]), "relocations": int(counters[1]),
+                "compactions": int(counters[2])}
+        return uid[:cap], idx[:cap], info
+
+    def _resident_args(self, pod, nodes, pdb_allowed):
+        pod = np.ascontiguousarray(np.asarray(pod, dtype=abi.POD_DTYPE).reshape(1))
+        nodes = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32)
+        nc = self.num_nodes if nodes is None else len(nodes)
+        pdb = np.ascontiguousarray(pdb_allowed if pdb_allowed is not None else [], dtype=np.int32)
+        return pod, nodes, nc, pdb
+
+    def select_victims_resident(self, pod: np.ndarray, priority: int, pdb_allowed=None, nodes=None,
+                                quota_rule: bool = True, entries: int | None = None):
+        """kg_pods_select_victims_resident: SelectVictimsOnNode over the resident table, unfused.  nodes = None: every
+        node slot.  entries: the candidates' resident entries (room of the per-entry outputs; default: the table's live
+        count, enough for candidates named once).  Returns (reject int32[C], violating int32[C], potential int32[C],
+        entry flags uint8[E], entry rank int32[E]): the per-entry arrays in candidate order, then the caller's list
+        order; flags = abi.ENTRY_POTENTIAL | ENTRY_VIOLATING | ENTRY_VICTIM, rank = the place in reprieve order or -1."""
+        pod, nodes, nc, pdb = self._resident_args(pod, nodes, pdb_allowed)
+        if entries is None:
+            entries = self.read_bound_pods(0)[2]["live"] if self.num_nodes else 0
+        rej, nvio, npot = (np.zeros(max(nc, 1), dtype=np.int32) for _ in range(3))
+        ef, er = np.zeros(max(entries, 1), dtype=np.uint8), np.full(max(entries, 1), -1, dtype=np.int32)
+        check(self.lib, self.lib.kg_pods_select_victims_resident(
+            self.h, ptr(pod), int(priority), abi.PREEMPT_RULE_QUOTA if quota_rule else 0, nc, ptr(nodes), ptr(pdb),
+            len(pdb), ptr(rej), ptr(nvio), ptr(npot), ptr(ef), ptr(er), int(entries)))
+        return rej[:nc], nvio[:nc], npot[:nc], ef[:entries], er[:entries]
+
+    def preempt_resident(self, pod: np.ndarray, priority: int, pdb_allowed=None, nodes=None, quota_rule: bool = True,
+                         want_reject: bool = False, victims_cap: int = 1024):
+        """kg_pods_preempt_resident: the dry run over the resident table and SelectCandidate's pick in one call.
+        Returns (pick, victim uids int64[n_victims], victim caller-list indices int32[n_victims]) in Victims.Pods order,
+        with want_reject also the int32[C] status words.  victims_cap: the room for the winner's victims; below the
+        longest resident list among the candidates it is refused.  The engine's state is unchanged."""
+        pod, nodes, nc, pdb = self._resident_args(pod, nodes, pdb_allowed)
+        pick = np.zeros(1, dtype=abi.PREEMPT_PICK_DTYPE)
+        uid, idx = np.zeros(max(victims_cap, 1), np.int64), np.zeros(max(victims_cap, 1), np.int32)
+        rej = np.zeros(max(nc, 1), dtype=np.int32) if want_reject else None
+        check(self.lib, self.lib.kg_pods_preempt_resident(
+            self.h, ptr(pod), int(priority), abi.PREEMPT_RULE_QUOTA if quota_rule else 0, nc, ptr(nodes), ptr(pdb),
+            len(pdb), ptr(pick), ptr(uid), ptr(idx), int(victims_cap), ptr(rej)))
+        nv = int(pick[0]["n_victims"])
+        out = (pick[0], uid[:nv].copy(), idx[:nv].copy())
+        return out + (rej[:nc],) if want_reject else out
+
     def evaluate_reservation(self, pod: np.ndarray) -> dict:
         """The exact pass's evaluation of one pod on every node (kg_pods_evaluate_reservation): per node pass,
         nominated slot, raw Reservation score, restore state (has_state, matched slots, restored Requested /

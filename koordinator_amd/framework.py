@@ -500,6 +500,14 @@ class Scheduler:
                 else np.zeros(0, dtype=abi.POD_DTYPE))
         return (pick, pods, *rest)
 
+    def post_filter(self, pod: np.ndarray, priority: int, pdb_allowed=None, nodes=None, quota_rule: bool = True, **kw):
+        """PostFilter over the resident bound-pod table (Engine.set_bound_pods feeds it; kg_pods_preempt_resident):
+        the canPreempt selection, the MoreImportantPod order, the PDB split, the dry run and the pick on the device.
+        nodes = None: every node is a candidate, as Koordinator's evaluator asks.  Returns (pick, uids of the victims on
+        pick["node_idx"] in Victims.Pods order); pick["candidate"] = -1 and no uids when nobody can make room."""
+        pick, uids, _idx, *rest = self.engine.preempt_resident(pod, priority, pdb_allowed, nodes, quota_rule, **kw)
+        return (pick, uids, *rest)
+
     def schedule_pods(self, pods: np.ndarray):
         return self.engine.schedule(pods)
 
