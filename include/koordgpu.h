@@ -819,6 +819,36 @@ int kg_debug_numa_merge(kg_engine* e, const int64_t* cases, int64_t n, int64_t* 
  * the number of (pod, node) pairs where feasibility or total score differ (must be 0). */
 int kg_debug_eval_paths(kg_engine* e, int64_t* mismatches);
 
+/* Debug (added within ABI 18; test hooks, not product paths — like the loopback hook, no scheduler calls them): the
+ * round engine's wide pass and merge, read back.
+ *
+ * kg_debug_round_records runs one round's eval_round and local merge over the staged pods [first, first + nb),
+ * nb <= batch_pods, against the table as it stands — the launches a round makes, on the engine stream, round slot 0 —
+ * and copies back what they wrote.  Neither kernel writes the node table; nothing is assumed.
+ *   out_geom    int64[KG_DBG_GEOM_WORDS]: nodes per tile, tiles per tile group, 1 when the lists are tile-group
+ *               lists (0: tile lists), lists per pod, words per list, keys per record (kC), score_bits, 0
+ *               (written before the buffer check, so a first call with lists_cap_words = 0 sizes the buffer)
+ *   out_lists   uint64[nb][lists per pod][words per list], lists_cap_words words available
+ *   out_records uint64[nb][kC + 1]: the record's keys (descending, 0-padded), then its bound ub
+ * A key is score << 32 | ~node index (32 bits); 0 = no candidate.
+ * KG_E_UNSUPPORTED: NUMA, DeviceShare, Reservation / exact-pass profiles, several ranks.  KG_E_INVALID: a range outside
+ * the staged queue or longer than a round, a lists buffer too small.
+ *
+ * kg_debug_merge merges caller-given lists: lists = uint64[n_pods][n_lists][list_len], out_records as above.
+ *   variant 0  the per-wavefront merge, through the round's own list-count dispatch (n_lists <= 512, list_len 8)
+ *   variant 1  the per-block merge of tile lists (n_lists <= 1024, list_len 8)
+ *   variant 2  the per-block merge of rank records (n_lists <= 128): list_len = 128 words per record, keys in words
+ *              [0, kC), the record's ub in word kC
+ * The lists must obey the kernels' contract: unique keys; list l covers lower node indices than list l + 1; within one
+ * score, positions ascend in node index.  Node indices at or past the engine's capacity are legal.  Checked on the
+ * host, KG_E_INVALID without a launch: a key whose score needs more than the engine's score_bits, a list count
+ * or length the variant does not take. */
+#define KG_DBG_GEOM_WORDS 8
+int kg_debug_round_records(kg_engine* e, int64_t first, int64_t nb, int64_t* out_geom, uint64_t* out_lists,
+                           int64_t lists_cap_words, uint64_t* out_records);
+int kg_debug_merge(kg_engine* e, int variant, const uint64_t* lists, int64_t n_pods, int64_t n_lists, int64_t list_len,
+                   uint64_t* out_records);
+
 /* Diagnostic builds (-DKG_STAMPS) only: copies the in-kernel (s_memtime, s_memrealtime) stamps, uint64[4][32][2],
  * then the last resolver launch's per-pod (s_memtime, path bits, sub-phase stamps), uint64[64][6], then the NUMA
  * hint-merge counters (merges, all-permutation fallback passes), uint64[2]: 258 + 384 words in all. */

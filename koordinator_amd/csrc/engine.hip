@@ -4889,6 +4889,27 @@ bool merge_block() {
   return on;
 }
 
+// One wavefront per pod: merge_wave<L, ll> for the list count, L lists per lane (nl ≤ 8·kWave, ll = kR or kRG).  The
+// round and the kg_debug_merge hook share this dispatch.
+void launch_merge_wave(const DevTable& T, const EvalParams& P, const uint64_t* lists, int nl, int ll, int nb,
+                       const int32_t* poison, uint64_t* dst, hipStream_t st) {
+  const unsigned blocks = (unsigned)((nb + 3) / 4);
+  const int64_t ps = (int64_t)nl * ll;
+#define KG_MW(LW, LLV) merge_wave<LW, LLV><<<blocks, kWave * 4, 0, st>>>(T, P, lists, ps, nl, nb, poison, dst)
+#define KG_MW_L(LLV)                    \
+  if (nl <= kWave) KG_MW(1, LLV);       \
+  else if (nl <= 2 * kWave) KG_MW(2, LLV); \
+  else if (nl <= 4 * kWave) KG_MW(4, LLV); \
+  else KG_MW(8, LLV);
+  if (ll == kRG) {
+    KG_MW_L(kRG)
+  } else {
+    KG_MW_L(kR)
+  }
+#undef KG_MW_L
+#undef KG_MW
+}
+
 void launch_merge_local(kg_engine* e, const RoundGeom& g, int nb, int slot, hipStream_t st) {
   uint64_t* dst = e->n_ranks > 1 ? gathered_slot(e, g, slot) + (size_t)e->rank * g.B * kCandStride : cand_slot(e, g, slot);
   const int nl = eval_lists(e, g);
@@ -4897,22 +4918,7 @@ void launch_merge_local(kg_engine* e, const RoundGeom& g, int nb, int slot, hipS
   const bool grp = !e->numa_on && !e->ds_on && eval_combine(g);
   const int ll = grp ? kRG : kR;
   if (!e->numa_on && !e->ds_on && !merge_block()) {  // (r4) one wavefront per pod
-    const unsigned blocks = (unsigned)((nb + 3) / 4);
-    const int64_t ps = (int64_t)nl * ll;
-#define KG_MW(LW, LLV) \
-  merge_wave<LW, LLV><<<blocks, kWave * 4, 0, st>>>(e->T, e->P, lists_slot(e, g, slot), ps, nl, nb, poison_ptr(e), dst)
-#define KG_MW_L(LLV)                    \
-  if (nl <= kWave) KG_MW(1, LLV);       \
-  else if (nl <= 2 * kWave) KG_MW(2, LLV); \
-  else if (nl <= 4 * kWave) KG_MW(4, LLV); \
-  else KG_MW(8, LLV);
-    if (grp) {
-      KG_MW_L(kRG)
-    } else {
-      KG_MW_L(kR)
-    }
-#undef KG_MW_L
-#undef KG_MW
+    launch_merge_wave(e->T, e->P, lists_slot(e, g, slot), nl, ll, nb, poison_ptr(e), dst, st);
     return;
   }
   merge_round<false><<<nb, kMergeThreads, 0, st>>>(e->T, e->P, lists_slot(e, g, slot), (int64_t)nl * ll, ll, nl, ll,
@@ -5171,9 +5177,13 @@ int prepare_rounds(kg_engine* e, RoundGeom& g) {
   if (int rc = sync_static(e)) return rc;
   g = geometry(e);
   if (g.N > kMaxNodes) return fail(KG_E_UNSUPPORTED, "n_nodes %lld > %lld", (long long)g.N, (long long)kMaxNodes);
-  if (g.nt_local > kMergeThreads * kMergeChunks)
-    return fail(KG_E_UNSUPPORTED, "%lld nodes per rank exceed one merge block (%d)", (long long)g.shard,
-                kMergeThreads * kMergeChunks * kTile);
+  // the merge's capacity in lists per pod: one merge_round block holds kMergeThreads·kMergeChunks tile lists (the NUMA
+  // and DeviceShare passes, KG_MERGE=block), one merge_wave wavefront 8·kWave tile or tile-group lists — every shard
+  // of at most kMaxNodes nodes, so the node-count bound above is the round engine's only one
+  const bool block_merge = e->numa_on || e->ds_on || merge_block();
+  if (eval_lists(e, g) > (block_merge ? kMergeThreads * kMergeChunks : 8 * kWave))
+    return fail(KG_E_UNSUPPORTED, "%lld nodes per rank exceed one merge %s (%d lists per pod)", (long long)g.shard,
+                block_merge ? "block" : "wavefront", block_merge ? kMergeThreads * kMergeChunks : 8 * kWave);
   if (e->ds_on && resolve_ds_lds_bytes(g, g.B, e->nq, e->n_ranks > 1) > kMaxLds)
     return fail(KG_E_UNSUPPORTED, "DeviceShare resolver LDS %zu B > %zu B: fewer nodes or a smaller batch_pods",
                 resolve_ds_lds_bytes(g, g.B, e->nq, e->n_ranks > 1), kMaxLds);
@@ -7177,6 +7187,94 @@ int kg_debug_eval_paths(kg_engine* e, int64_t* mismatches) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   b.release();
   return 0;
+}
+
+// kg_debug_round_records / kg_debug_merge: the round's wide pass and merge read back for the component tests
+// (tests/test_round_records.py).  Neither is a product path.
+int kg_debug_round_records(kg_engine* e, int64_t first, int64_t nb, int64_t* out_geom, uint64_t* out_lists,
+                           int64_t lists_cap_words, uint64_t* out_records) {
+  if (!e || !out_geom || !out_lists || !out_records) return fail(KG_E_INVALID, "null argument");
+  if (e->numa_on || e->ds_on || e->exact_on || e->n_ranks > 1)
+    return fail(KG_E_UNSUPPORTED, "the Fit + LoadAware round engine on one rank only");
+  RoundGeom g;
+  if (int rc = prepare_rounds(e, g)) return rc;
+  if (first < 0 || nb < 1 || nb > g.B || first + nb > e->n_staged)
+    return fail(KG_E_INVALID, "pods [%lld, %lld): a round of at most %d staged pods (%lld staged)", (long long)first,
+                (long long)(first + nb), g.B, (long long)e->n_staged);
+  const int nl = eval_lists(e, g), ll = eval_combine(g) ? kRG : kR;
+  const int64_t geom[KG_DBG_GEOM_WORDS] = {kETile, kEW, eval_combine(g) ? 1 : 0, nl, ll, kC, e->P.score_bits, 0};
+  std::memcpy(out_geom, geom, sizeof(geom));
+  const size_t list_words = (size_t)nb * nl * ll;
+  if ((int64_t)list_words > lists_cap_words)
+    return fail(KG_E_INVALID, "the lists take %zu words, the buffer holds %lld", list_words, (long long)lists_cap_words);
+  HIP_TRY(hipMemsetAsync(e->cursor.p + CTL_POISON, 0, sizeof(int64_t), e->stream));
+  launch_eval(e, g, first, (int)nb, 0, e->stream);
+  HIP_TRY(hipGetLastError());
+  launch_merge_local(e, g, (int)nb, 0, e->stream);
+  HIP_TRY(hipGetLastError());
+  std::vector<uint64_t> rec((size_t)nb * kCandStride);
+  HIP_TRY(hipMemcpyAsync(out_lists, lists_slot(e, g, 0), list_words * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(rec.data(), cand_slot(e, g, 0), rec.size() * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (int64_t p = 0; p < nb; ++p)
+    std::memcpy(out_records + (size_t)p * (kC + 1), rec.data() + (size_t)p * kCandStride, (kC + 1) * 8);
+  return 0;
+}
+
+int kg_debug_merge(kg_engine* e, int variant, const uint64_t* lists, int64_t n_pods, int64_t n_lists, int64_t list_len,
+                   uint64_t* out_records) {
+  if (!e || variant < 0 || variant > 2 || n_pods < 0 || n_pods > (1 << 16) || (n_pods > 0 && (!lists || !out_records)))
+    return fail(KG_E_INVALID, "bad argument");
+  const int64_t cap = variant == 0 ? 8 * kWave : variant == 1 ? kMergeThreads * kMergeChunks : kMergeThreads * kMergeChunks / (kC / 8);
+  if (n_lists < 1 || n_lists > cap)
+    return fail(KG_E_INVALID, "%lld lists per pod: variant %d merges 1..%lld", (long long)n_lists, variant, (long long)cap);
+  if (variant == 2 ? list_len != kCandStride : (list_len != kR && list_len != kRG))
+    return fail(KG_E_INVALID, "list length %lld: variant %d is compiled for %d%s", (long long)list_len, variant,
+                variant == 2 ? kCandStride : kR, variant != 2 && kRG != kR ? " and the tile-group length" : "");
+  if (n_pods == 0) return 0;
+  // merge_round's histogram is indexed by the score: a key outside the engine's score range is refused here
+  const int64_t keys_per_list = variant == 2 ? kC : list_len;
+  const size_t words = (size_t)n_pods * n_lists * list_len;
+  for (size_t l = 0; l < (size_t)n_pods * n_lists; ++l)
+    for (int64_t r = 0; r < keys_per_list; ++r)
+      if ((lists[l * list_len + r] >> 32) >> e->P.score_bits)
+        return fail(KG_E_INVALID, "list %zu key %lld: score %llu needs more than score_bits = %d", l, (long long)r,
+                    (unsigned long long)(lists[l * list_len + r] >> 32), e->P.score_bits);
+  DevBuf<uint64_t> din, dout;
+  DevBuf<int32_t> dzero;
+  auto done = [&](int rc) {
+    din.release();
+    dout.release();
+    dzero.release();
+    return rc;
+  };
+  if (int rc = din.ensure(words)) return done(rc);
+  if (int rc = dout.ensure((size_t)n_pods * kCandStride)) return done(rc);
+  if (int rc = dzero.ensure(2)) return done(rc);
+  hipError_t he = hipMemcpyAsync(din.p, lists, words * 8, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(dout.p, 0, (size_t)n_pods * kCandStride * 8, e->stream);
+  if (he == hipSuccess) he = hipMemsetAsync(dzero.p, 0, 8, e->stream);
+  if (he == hipSuccess) {
+    if (variant == 0)
+      launch_merge_wave(e->T, e->P, din.p, (int)n_lists, (int)list_len, (int)n_pods, dzero.p, dout.p, e->stream);
+    else if (variant == 1)
+      merge_round<false><<<(unsigned)n_pods, kMergeThreads, 0, e->stream>>>(e->T, e->P, din.p, n_lists * list_len, list_len,
+                                                                           (int)n_lists, (int)list_len, (int)n_pods,
+                                                                           dzero.p, dout.p);
+    else
+      merge_round<true><<<(unsigned)n_pods, kMergeThreads, 0, e->stream>>>(e->T, e->P, din.p, n_lists * kCandStride,
+                                                                          kCandStride, (int)n_lists, kC, (int)n_pods,
+                                                                          dzero.p, dout.p);
+    he = hipGetLastError();
+  }
+  std::vector<uint64_t> rec((size_t)n_pods * kCandStride);
+  if (he == hipSuccess) he = hipMemcpyAsync(rec.data(), dout.p, rec.size() * 8, hipMemcpyDeviceToHost, e->stream);
+  const hipError_t hs = hipStreamSynchronize(e->stream);  // before the buffers go, whatever was queued
+  if (he == hipSuccess) he = hs;
+  if (he != hipSuccess) return done(fail(KG_E_DEVICE, "kg_debug_merge: %s", hipGetErrorString(he)));
+  for (int64_t p = 0; p < n_pods; ++p)
+    std::memcpy(out_records + (size_t)p * (kC + 1), rec.data() + (size_t)p * kCandStride, (kC + 1) * 8);
+  return done(0);
 }
 
 int kg_debug_stamps(kg_engine* e, uint64_t* out) {

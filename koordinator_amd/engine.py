@@ -369,6 +369,36 @@ class Engine:
         check(self.lib, self.lib.kg_debug_eval_paths(self.h, ptr(out)))
         return int(out[0])
 
+    def debug_round_records(self, first: int, nb: int):
+        """One round's wide pass and local merge over the staged pods [first, first + nb), read back
+        (kg_debug_round_records; a test hook, the table is left as it was).  Returns (geom, lists, records): geom a dict
+        over abi.DBG_GEOM_FIELDS, lists uint64[nb, n_lists, list_len], records uint64[nb, kc + 1] (keys, then ub)."""
+        geom = np.zeros(abi.DBG_GEOM_WORDS, dtype=np.int64)
+        probe = np.zeros(1, dtype=np.uint64)
+        # sizing call: the geometry is written before the (empty) lists buffer is refused
+        rc = self.lib.kg_debug_round_records(self.h, int(first), int(nb), ptr(geom), ptr(probe), 0, ptr(probe))
+        g = dict(zip(abi.DBG_GEOM_FIELDS, (int(x) for x in geom)))
+        if rc == 0 or g["n_lists"] <= 0:
+            check(self.lib, rc)
+            raise RuntimeError("kg_debug_round_records accepted an empty lists buffer")
+        lists = np.zeros((int(nb), g["n_lists"], g["list_len"]), dtype=np.uint64)
+        records = np.zeros((int(nb), g["kc"] + 1), dtype=np.uint64)
+        check(self.lib, self.lib.kg_debug_round_records(self.h, int(first), int(nb), ptr(geom), ptr(lists), lists.size,
+                                                        ptr(records)))
+        return g, lists, records
+
+    def debug_merge(self, variant: int, lists: np.ndarray, kc: int = 64) -> np.ndarray:
+        """The merge kernels on caller-given lists uint64[n_pods, n_lists, list_len] (kg_debug_merge; a test hook):
+        variant 0 the per-wavefront merge, 1 the per-block merge of tile lists, 2 the per-block merge of rank records.
+        Returns the records uint64[n_pods, kc + 1] (keys, then ub)."""
+        lists = np.ascontiguousarray(lists, dtype=np.uint64)
+        if lists.ndim != 3:
+            raise ValueError("lists: uint64[n_pods, n_lists, list_len]")
+        n_pods, n_lists, list_len = lists.shape
+        out = np.zeros((n_pods, kc + 1), dtype=np.uint64)
+        check(self.lib, self.lib.kg_debug_merge(self.h, int(variant), ptr(lists), n_pods, n_lists, list_len, ptr(out)))
+        return out
+
     def filter_preemption(self, pod: np.ndarray, node: int, victims: np.ndarray, slots=None, minors=None) -> int:
         """The preemption dry run's Filter of `pod` on node `node` with `victims` removed (kg_pods_filter_preemption):
         KG_REJECT_* bits, 0 = fits.  slots[k]: the node's reservation slot victim k was allocated from (-1 = none);

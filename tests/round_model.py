@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from koordinator_amd import abi, framework, synth
 from oracle import oracle
 
 
@@ -49,6 +50,70 @@ def tile_record(keys: np.ndarray, tile: int, kr: int, kc: int):
             ub = max(ub, min(lst))
         union.extend(lst)
     return _top_with_ub(union, kc, ub)
+
+
+# ---- the two-level lists of eval_round (the record invariant) ---------------------------------------
+# Geometry (kg_debug_round_records' out_geom): a tile is `tile_nodes` consecutive nodes, a group `group_tiles`
+# consecutive tiles.  A tile list is the tile's kr largest keys in ascending node order; a group list (the combined
+# case) is the list_len largest keys of its tiles' lists in descending key order; both are zero-padded at the tail.
+# All arrays are uint64; a key is score << 32 | ~node, so within one score a larger key is a lower node index.
+
+def _zeros_last(lists: np.ndarray) -> np.ndarray:
+    order = np.argsort(lists == 0, axis=1, kind="stable")
+    return np.take_along_axis(lists, order, axis=1)
+
+
+def tile_lists(keys: np.ndarray, tile_nodes: int, kr: int) -> np.ndarray:
+    """uint64[n_tiles, kr]: per tile of `keys` (node order) its kr largest keys, in ascending node order."""
+    keys = np.asarray(keys, dtype=np.uint64)
+    n_tiles = max(1, -(-len(keys) // tile_nodes))
+    k2 = np.zeros(n_tiles * tile_nodes, dtype=np.uint64)
+    k2[:len(keys)] = keys
+    k2 = k2.reshape(n_tiles, tile_nodes)
+    pos = np.argsort(k2, axis=1, kind="stable")[:, -kr:]  # positions of the kr largest (non-zero keys are unique)
+    pos.sort(axis=1)  # ascending position = ascending node index
+    return _zeros_last(np.take_along_axis(k2, pos, axis=1))
+
+
+def group_lists(tlists: np.ndarray, group_tiles: int, list_len: int) -> np.ndarray:
+    """uint64[n_groups, list_len]: per group of `group_tiles` tile lists the list_len largest keys, descending."""
+    n_tiles, kr = tlists.shape
+    n_groups = -(-n_tiles // group_tiles)
+    g = np.zeros((n_groups * group_tiles, kr), dtype=np.uint64)
+    g[:n_tiles] = tlists
+    g = np.sort(g.reshape(n_groups, group_tiles * kr), axis=1)[:, ::-1]
+    return np.ascontiguousarray(g[:, :list_len])
+
+
+def round_lists(keys: np.ndarray, geom: dict) -> np.ndarray:
+    """The lists eval_round hands the merge for one pod: tile lists, or group lists when geom says combined.  (A group
+    list is no longer than a tile list, so its keys are the group's list_len largest whatever the tile lists' length:
+    tile lists of list_len keys model it.)"""
+    tl = tile_lists(keys, geom["tile_nodes"], geom["list_len"])
+    return group_lists(tl, geom["group_tiles"], geom["list_len"]) if geom["combined"] else tl
+
+
+def lists_record(lists: np.ndarray, kc: int):
+    """merge_wave / merge_round<false> on one pod's lists: (top-kc keys descending, ub).  A full list bounds its
+    unseen nodes by its minimum; a key of the union left out bounds by itself + 1."""
+    lists = np.asarray(lists, dtype=np.uint64)
+    full = (lists != 0).all(axis=1)
+    ub_in = int(lists[full].min(axis=1).max()) if full.any() else 0
+    nz = np.sort(lists[lists != 0])[::-1]
+    top = [int(k) for k in nz[:kc]]
+    ub = max(ub_in, int(nz[kc]) + 1) if len(nz) > kc else ub_in
+    return top, ub
+
+
+def rank_records(records: np.ndarray, kc: int):
+    """merge_round<true> on records uint64[n, > kc] (keys in words [0, kc), ub in word kc)."""
+    return merge_ranks([([int(k) for k in r[:kc] if k], int(r[kc])) for r in records], kc)
+
+
+def round_record(keys: np.ndarray, geom: dict):
+    """(lists, (top, ub)) of one pod whose per-node keys are `keys`, for the engine geometry `geom`."""
+    lists = round_lists(keys, geom)
+    return lists, lists_record(lists, geom["kc"])
 
 
 def merge_ranks(records, kc: int):
@@ -136,3 +201,23 @@ class RoundModel:
                 else:
                     prev_mod = cur
         return out_node, out_score
+
+
+# ---- inputs the list / record tests share -------------------------------------------------------------------------
+def model_geometry(n, tile_nodes=128, group_tiles=8, combine_tiles=128, list_len=8, kc=64, score_bits=8):
+    """The geometry kg_debug_round_records reports for n nodes with the engine's default constants (the GPU tests take
+    theirs from the device; these tests only need a self-consistent one)."""
+    nte = max(1, -(-n // tile_nodes))
+    comb = nte >= combine_tiles
+    return {"tile_nodes": tile_nodes, "group_tiles": group_tiles, "combined": int(comb),
+            "n_lists": -(-nte // group_tiles) if comb else nte, "list_len": list_len, "kc": kc,
+            "score_bits": score_bits}
+
+
+def tie_cluster(n):
+    """Every node alike (the cluster of test_ties_resolve_to_lowest_index): every pod ties on every node."""
+    nodes = np.repeat(framework.make_node({"cpu": "16", "memory": "64Gi"}), n)
+    metrics = np.repeat(framework.make_node_metric(update_time_ns=synth.T0_NS,
+                                                   node_usage={"cpu": "1", "memory": "1Gi"}), n)
+    return synth.Cluster(nodes, metrics, np.zeros(0, dtype=abi.POD_DTYPE), np.zeros(0, dtype=np.int32),
+                         synth.T0_NS + 10**9)

@@ -200,6 +200,37 @@ def test_schedule_parity_pipeline_depths(depth, batch):
     _parity(cfg, cl, synth.make_pods(2500, seed=25))
 
 
+def _tie_heavy_cluster(n):
+    nodes = np.concatenate([framework.make_node({"cpu": "16", "memory": "64Gi"}) for _ in range(n)])
+    metrics = np.concatenate([framework.make_node_metric(update_time_ns=synth.T0_NS,
+                                                         node_usage={"cpu": "1", "memory": "1Gi"}) for _ in range(n)])
+    return synth.Cluster(nodes, metrics, np.zeros(0, dtype=abi.POD_DTYPE), np.zeros(0, dtype=np.int32),
+                         synth.T0_NS + 10**9)
+
+
+@pytest.mark.parametrize("depth", [1, 2, 4])
+@pytest.mark.parametrize("weights", [(41, 41), (40, 41), (1000, 3000)], ids=lambda w: f"{w[0]}+{w[1]}")
+def test_schedule_parity_wide_scores(weights, depth):
+    """Score widths the default weights never reach: totals up to 8,200 need 14 bits, so the resolver's packed 32-bit
+    key (score << 19 | ~node) no longer holds them and it compares 64-bit keys; 8,100 is the last total that fits (13
+    bits); 400,000 needs 19.  The wide pass bisects its threshold over the wider range and the merge selects by radix.
+    On the random and on the tie-heavy cluster, at every pipeline depth; each run must have re-scored modified rows
+    (the slow-path counter), or the resolver's modified-row maximum — the 64-bit one — never ran."""
+    prof = framework.Profile(score={framework.NODE_RESOURCES_FIT: weights[0], framework.LOAD_AWARE: weights[1]})
+    cfg = framework.build_config(profile=prof, batch_pods=32, pods_per_wave=8, pipeline_depth=depth)
+    for cl, pods in ((synth.make_cluster(1500, seed=23), synth.make_pods(4000, seed=24)),
+                     (_tie_heavy_cluster(300), synth.make_pods(2500, seed=25))):
+        _, stats = _parity(cfg, cl, pods)
+        assert stats["reserved"][0] > 0, f"{cl.n} nodes: no pod took the resolver's slow path"
+
+
+@pytest.mark.parametrize("n_nodes", [131_073, 262_145])
+def test_schedule_parity_large_tables(n_nodes):
+    """More than 131,072 nodes: 4 group lists per lane of the merge; more than 262,144: 8 — under the real resolver,
+    whose node bitmap grows with the table.  A 256-pod queue at the default depth."""
+    _parity(framework.build_config(), synth.make_cluster(n_nodes, seed=n_nodes), synth.make_pods(256, seed=7), threads=16)
+
+
 def test_schedule_parity_profile_variants():
     cl = synth.make_cluster(800, seed=31)
     pods = synth.make_pods(2000, seed=32)
