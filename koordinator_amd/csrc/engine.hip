@@ -32,6 +32,7 @@
 #include "numa_dev.h"
 #include "ds_dev.h"
 #include "round_ctl.h"
+#include "round_lds.h"
 #include "rsv_dev.h"
 
 using namespace kg;
@@ -51,23 +52,16 @@ constexpr int kTile = kWave * kNPT;   // 256 nodes per tile
 constexpr int kENPT = KG_EVAL_NPT;
 constexpr int kETile = kWave * kENPT;
 constexpr int kEW = KG_EVAL_EW;
-constexpr int kR = 8;                 // candidates kept per (pod, tile)
 #ifndef KG_GROUP_KEYS
 #define KG_GROUP_KEYS 8
 #endif
 constexpr int kRG = KG_GROUP_KEYS;    // (r5) candidates kept per (pod, tile group of kEW tiles): the merge's input
 static_assert(kRG % 2 == 0 && kRG <= kR, "group lists: an even count of at most kR keys");
 constexpr int kEvalWaves = 4;         // waves (tiles) per eval block
-constexpr int kC = 64;                // merged candidates per pod (> any modified-set size: kC > kMaxB - 1)
-constexpr int kStaged = 3;            // hoisted rows of each pod's best candidates shipped with its record
-constexpr int kRecRows = 72;          // record layout (uint64 words): [0,kC) keys, [kC] ub, [72, 72+3·17) rows
-constexpr int kCandStride = 128;      // per-pod record: 1 KiB (a 16-B multiple, for LDS-DMA)
 constexpr int kMergeThreads = 256;
 constexpr int kMergeChunks = 4;       // chunks of 8 keys per merge thread: ≤ 1024 tile lists = 262144 nodes per rank
 constexpr double kAlgoBytesPerNode = 76.0;  // SURVEY §8(d) b_node for C1-C3: Fit 56 B + LoadAware 20 B
 constexpr int64_t kMaxBatchRounds = 256;  // rounds launched between two host synchronisations
-constexpr int64_t kMaxNodes = 1 << 19;  // resolver LDS: N/8-byte bitmap (≤ 64 KiB) + the round's records (≤ 64 KiB)
-static_assert(kRecRows + kStaged * kEvalRowWords <= kCandStride, "record layout");
 
 thread_local std::string g_err;
 
@@ -920,7 +914,6 @@ __global__ __launch_bounds__(kWave * 4) void merge_wave(DevTable T, EvalParams P
 // reference-shaped eval_node with the EvalParams copy in LDS behind an opaque pointer: its runtime weight / flag
 // tests then stay inside the (rare) branch instead of being hoisted as loop-invariant scalar masks that crowd the
 // resolver's scalar registers.
-constexpr int kParWords = (int)((sizeof(EvalParams) + 7) / 8);
 template <int PF>
 __device__ __forceinline__ uint64_t mod_key(const EvalRow& er, uint32_t node, const DevPod& p, const EvalParams& P,
                                             const uint64_t* s_par) {
@@ -1111,12 +1104,13 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
   const int lane = threadIdx.x;
   // the serial chain outranks the wide pass's waves when they share a SIMD
   __builtin_amdgcn_s_setprio(3);
-  uint64_t* s_cand = smem;                                            // [nb][kCandStride]
-  uint64_t* s_podw = s_cand + (size_t)nb * kCandStride;               // [nb] DevPod (kPodWords words)
-  uint64_t* s_par = s_podw + (size_t)nb * kPodWords;                  // [kParWords] EvalParams (rare-path copy)
-  uint32_t* s_hash = reinterpret_cast<uint32_t*>(s_par + kParWords);  // [kModHash]
-  uint32_t* s_prevn = s_hash + kModHash;                              // [kMaxMod] earlier rounds' nodes
-  uint32_t* bitmap = s_prevn + kMaxMod;                               // [bitmap_words]
+  const ResolveLds L = resolve_lds(nb, bitmap_words);
+  uint64_t* s_cand = lds_at<uint64_t>(smem, L.cand);
+  uint64_t* s_podw = lds_at<uint64_t>(smem, L.pods);
+  uint64_t* s_par = lds_at<uint64_t>(smem, L.par);
+  uint32_t* s_hash = lds_at<uint32_t>(smem, L.hash);
+  uint32_t* s_prevn = lds_at<uint32_t>(smem, L.prevn);
+  uint32_t* bitmap = lds_at<uint32_t>(smem, L.bitmap);
   {
     uint64_t pw[kParWords] = {};
     __builtin_memcpy(pw, &P, sizeof(P));
@@ -1330,46 +1324,10 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
 // own register copy, lane = slot) and publishes the row's new state; each helper advances its own register copy of
 // the rows to its lag from those states, and the chain reads them only to re-score a recent winner (rare: ~5 % of C3
 // pods).
-constexpr int kHelpers = 5;                        // helper waves
-constexpr int kLag = kHelpers + 1;                 // helper(j) scores pod j on the table after pods ≤ j − kLag
-constexpr int kTop = kLag;                         // candidates per pod handed to the chain (> |S| = kLag − 1)
 constexpr int kMwThreads = kWave * (2 + kHelpers);  // the chain, the keeper, the helpers
 constexpr uint32_t kTopMod = 0x80000000u;  // s_topx: a modified row (its slot in the low bits); otherwise the LDS
                                            // word offset of the candidate's round-start EvalRow
 constexpr int64_t kMwSpin = 1 << 24;       // bounded in-workgroup waits (an error instead of a hang on a bug)
-
-struct MwLayout {  // dynamic LDS carve; u64 arrays (word offsets), then u32 arrays (offsets from the u32 base)
-  uint32_t cand, podw, par, prow, toprow, state, top, u64_end;
-  uint32_t topx, win, wslot, nsl, ready, slot_node, slot_row, hash, prevn, sctl, u32_end;
-};
-__host__ __device__ inline MwLayout mw_layout(int nb) {
-  MwLayout L;
-  L.cand = 0;
-  L.podw = L.cand + (uint32_t)nb * kCandStride;
-  L.par = L.podw + (uint32_t)nb * kPodWords;
-  L.prow = L.par + kParWords;                          // earlier rounds' rows (slots < nP)
-  // slots of earlier rounds ≤ (depth − 1) · batch ≤ kMaxMod − nb (RoundGeom keeps depth · batch ≤ kMaxMod)
-  L.toprow = L.prow + (uint32_t)(kMaxMod - nb) * kEvalRowWords;  // rows of listed candidates past the staged ones
-  L.state = L.toprow + (uint32_t)nb * kTop * kEvalRowWords;  // the winner's row after pod j's assume
-  L.top = L.state + (uint32_t)nb * kEvalRowWords;
-  L.u64_end = L.top + (uint32_t)nb * kTop;
-  L.topx = 0;
-  L.win = L.topx + (uint32_t)nb * kTop;
-  L.wslot = L.win + (uint32_t)nb;
-  L.nsl = L.wslot + (uint32_t)nb;    // slots in use after pod j
-  L.ready = L.nsl + (uint32_t)nb;    // helper(j) done
-  L.slot_node = L.ready + (uint32_t)nb;
-  L.slot_row = L.slot_node + kMaxMod;   // LDS word offset of the slot's round-start row
-  L.hash = L.slot_row + kMaxMod;
-  L.prevn = L.hash + kModHash;
-  L.sctl = L.prevn + kMaxMod;  // [0] pods published, [1] chain ended, [2] abort, [3] nP, [4] error, [5] states kept
-  L.u32_end = L.sctl + 8;
-  return L;
-}
-inline size_t mw_lds_bytes(int nb) {
-  const MwLayout L = mw_layout(nb);
-  return (size_t)L.u64_end * 8 + (size_t)L.u32_end * 4;
-}
 
 // Hand-offs between the resolver's waves go through LDS only, and the LDS serves one wave's DS instructions in issue
 // order: a flag written after the data it guards is seen by another wave only after that data, and that wave's data
@@ -1432,13 +1390,13 @@ __global__ __launch_bounds__(kMwThreads) void resolve_mw(DevTable T0, const DevP
                                                          const int64_t* __restrict__ paux) {
   extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
   KG_STAMP(2, 0);
-  const MwLayout L = mw_layout(nb);
+  const MwLds L = mw_lds(nb);
   const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
   if (wave == 0) __builtin_amdgcn_s_setprio(3);  // the chain first, then its helpers, then any wide-pass wave
   else __builtin_amdgcn_s_setprio(2);
   uint64_t* s_cand = smem + L.cand;
   uint64_t* s_par = smem + L.par;
-  uint32_t* b32 = reinterpret_cast<uint32_t*>(smem + L.u64_end);
+  uint32_t* b32 = lds_at<uint32_t>(smem, L.u32);
   uint32_t* s_topx = b32 + L.topx;
   uint32_t* s_win = b32 + L.win;
   uint32_t* s_wslot = b32 + L.wslot;
@@ -1968,9 +1926,6 @@ __global__ __launch_bounds__(kWave* kEvalWaves) void eval_round_numa(DevTable T,
 // every modified row; best < ub ends the round early (as resolve_round).  The winner's owner lane runs
 // Reserve — the NUMA allocation with the exact cpuset (cpu accumulator); a failed Reserve leaves the pod
 // unplaced (RunReservePluginsUnreserve) and the node unchanged.
-constexpr int kNumaStaticWords = (int)(sizeof(NumaStatic) / 8), kNumaMutWords = (int)(sizeof(NumaMut) / 8);
-constexpr int kNumaPodWords = (int)(sizeof(NumaPod) / 8);
-
 __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTable NT, const DevPod* __restrict__ pods,
                                                              const NumaPod* __restrict__ npods,
                                                              int64_t* __restrict__ ctl, int64_t first, int nb,
@@ -1984,20 +1939,13 @@ __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTabl
                                                              int n_prev, int wait) {
   extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
   const int lane = threadIdx.x;
-  uint64_t* s_cand = smem;                                    // [nb][kCandStride]
-  uint64_t* s_podw = s_cand + (size_t)nb * kCandStride;       // [nb] DevPod
-  uint64_t* s_npw = s_podw + (size_t)nb * kPodWords;          // [nb] NumaPod
-  uint64_t* s_nsw = s_npw + (size_t)nb * kNumaPodWords;       // [kWave] NumaStatic of the modified rows
-  uint64_t* s_nmw = s_nsw + (size_t)kWave * kNumaStaticWords; // [kWave] NumaMut of the modified rows
-  uint32_t* s_prevn = reinterpret_cast<uint32_t*>(s_nmw + (size_t)kWave * kNumaMutWords);  // [kWave] earlier winners
-  uint32_t* bitmap = s_prevn + kWave;
-  for (int w = lane; w < nb * kCandStride; w += kWave) s_cand[w] = cand[w];
-  {
-    const uint64_t* pw = reinterpret_cast<const uint64_t*>(pods + first);
-    for (int w = lane; w < nb * kPodWords; w += kWave) s_podw[w] = pw[w];
-    const uint64_t* nw = reinterpret_cast<const uint64_t*>(npods + first);
-    for (int w = lane; w < nb * kNumaPodWords; w += kWave) s_npw[w] = nw[w];
-  }
+  const NumaLds L = numa_lds(nb, bitmap_words);
+  uint64_t* s_cand = lds_at<uint64_t>(smem, L.s.cand);
+  uint32_t* s_prevn = lds_at<uint32_t>(smem, L.prevn);
+  uint32_t* bitmap = lds_at<uint32_t>(smem, L.bitmap);
+  lds_stage(s_cand, cand, 0, nb, kCandStride, lane, kWave);
+  lds_stage(lds_at<uint64_t>(smem, L.s.pods), pods, first, nb, kPodWords, lane, kWave);
+  lds_stage(lds_at<uint64_t>(smem, L.s.npods), npods, first, nb, kNumaPodWords, lane, kWave);
   for (int w = lane; w < bitmap_words; w += kWave) bitmap[w] = 0;
   __syncthreads();
   // (r5) pipelined rounds: chain on the previous round's resolver (its rows, cursor, poison and winner list are
@@ -2009,10 +1957,10 @@ __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTabl
     return;
   }
   const uint64_t t_active = __builtin_amdgcn_s_memrealtime();  // the period decomposition's resolver time
-  const DevPod* s_pods = reinterpret_cast<const DevPod*>(s_podw);
-  const NumaPod* s_np = reinterpret_cast<const NumaPod*>(s_npw);
-  NumaStatic* s_ns = reinterpret_cast<NumaStatic*>(s_nsw);
-  NumaMut* s_nm = reinterpret_cast<NumaMut*>(s_nmw);
+  const DevPod* s_pods = lds_at<const DevPod>(smem, L.s.pods);
+  const NumaPod* s_np = lds_at<const NumaPod>(smem, L.s.npods);
+  NumaStatic* s_ns = lds_at<NumaStatic>(smem, L.s.ns);
+  NumaMut* s_nm = lds_at<NumaMut>(smem, L.s.nm);
   uint32_t midx = 0xFFFFFFFFu;
   Row mrow;
   mrow.flags = 0;
@@ -2174,22 +2122,12 @@ __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTabl
 // chain per pod becomes max(scorer, Reserve + one row) instead of their sum.  Same results as
 // resolve_round_numa: the scorer's key of Reserve(j - 1)'s slot is replaced by the reserver's, every other slot's state
 // is the one a sequential resolver would see.
-constexpr int kRowWords = (int)(sizeof(Row) / 8);
-static_assert(sizeof(Row) % 8 == 0, "Row in 8-byte words");
 constexpr int kNuma2Threads = 2 * kWave;
 // (r6) a row's view (make_view, ~3-4 k cycles on one lane) is built once per state and shared through LDS: the
-// reserver publishes the view of the state it commits, the scorer the views of the rows it stages
-constexpr int kViewWords = (int)(sizeof(NumaView) / 8);
-static_assert(sizeof(NumaView) % 8 == 0, "NumaView in 8-byte words");
-size_t numa2_extra_lds_bytes() {  // beyond resolve_numa_lds_bytes: slot Rows and views, reserver's NumaMut, keys, ...
-  return ((size_t)kWave * (kRowWords + kViewWords + 1 + 2) + kNumaMutWords + 4) * 8 + (size_t)kWave * 4 * 2 + 16 * 4;
-}
-// the rows (and views) of each pod's first kNumaPre candidates, read into LDS once per round (after the chain wait, so
-// an unmodified row's copy is current): the best unmodified candidate's staging then reads LDS instead of HBM and
+// reserver publishes the view of the state it commits, the scorer the views of the rows it stages.
+// The rows (and views) of each pod's first kNumaPre candidates are read into LDS once per round (after the chain wait,
+// so an unmodified row's copy is current): the best unmodified candidate's staging then reads LDS instead of HBM and
 // rebuilding its view on the serial path
-constexpr int kNumaPre = 2;
-constexpr int kPreWords = kRowWords + kNumaStaticWords + kNumaMutWords + kViewWords;
-size_t numa2_pre_lds_bytes(int nb) { return (size_t)nb * kNumaPre * kPreWords * 8; }
 
 __global__ __launch_bounds__(kNuma2Threads) void resolve_round_numa2(DevTable T, NumaTable NT,
                                                                       const DevPod* __restrict__ pods,
@@ -2205,30 +2143,24 @@ __global__ __launch_bounds__(kNuma2Threads) void resolve_round_numa2(DevTable T,
                                                                       int depth, int n_prev, int wait, int npre) {
   extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
   const int tid = threadIdx.x, wave = tid / kWave, lane = tid % kWave;
-  uint64_t* s_cand = smem;                                     // [nb][kCandStride]
-  uint64_t* s_podw = s_cand + (size_t)nb * kCandStride;        // [nb] DevPod
-  uint64_t* s_npw = s_podw + (size_t)nb * kPodWords;           // [nb] NumaPod
-  uint64_t* s_nsw = s_npw + (size_t)nb * kNumaPodWords;        // [kWave] NumaStatic of the slots
-  uint64_t* s_nmw = s_nsw + (size_t)kWave * kNumaStaticWords;  // [kWave] NumaMut of the slots (committed)
-  uint64_t* s_roww = s_nmw + (size_t)kWave * kNumaMutWords;    // [kWave] Row of the slots (committed)
-  uint64_t* s_vieww = s_roww + (size_t)kWave * kRowWords;      // [kWave] view of each slot's current state
-  uint64_t* s_rnmw = s_vieww + (size_t)kWave * kViewWords;     // the reserver's NumaMut after its Reserve
-  uint64_t* s_key = s_rnmw + kNumaMutWords;                    // [kWave] the scorer's keys of the current pod
-  uint64_t* s_affw = s_key + kWave;                            // [kWave][2] the scorer's affinities (NumaHint)
-  uint64_t* s_misc = s_affw + (size_t)kWave * 2;               // [4]: 0 = the current pod's e key (0 = none)
-  uint32_t* s_ver = reinterpret_cast<uint32_t*>(s_misc + 4);   // [kWave] slot state versions
-  uint32_t* s_node = s_ver + kWave;                            // [kWave] node of each slot
-  int32_t* s_c = reinterpret_cast<int32_t*>(s_node + kWave);   // [16] 0 nM, 1 stop, 4 timed out, 5 abort
-  uint32_t* bitmap = reinterpret_cast<uint32_t*>(s_c + 16);
-  uint32_t* s_prevn = bitmap + bitmap_words;                   // [kWave] earlier rounds' winners (prologue)
-  uint64_t* s_pre = reinterpret_cast<uint64_t*>(s_prevn + kWave);  // [nb][npre] Row, NumaStatic, NumaMut, view
-  for (int w = tid; w < nb * kCandStride; w += kNuma2Threads) s_cand[w] = cand[w];
-  {
-    const uint64_t* pw = reinterpret_cast<const uint64_t*>(pods + first);
-    for (int w = tid; w < nb * kPodWords; w += kNuma2Threads) s_podw[w] = pw[w];
-    const uint64_t* nw = reinterpret_cast<const uint64_t*>(npods + first);
-    for (int w = tid; w < nb * kNumaPodWords; w += kNuma2Threads) s_npw[w] = nw[w];
-  }
+  const Numa2Lds L = numa2_lds(nb, bitmap_words, npre);
+  uint64_t* s_cand = lds_at<uint64_t>(smem, L.s.cand);
+  uint64_t* s_nsw = lds_at<uint64_t>(smem, L.s.ns);
+  uint64_t* s_nmw = lds_at<uint64_t>(smem, L.s.nm);
+  uint64_t* s_roww = lds_at<uint64_t>(smem, L.row);
+  uint64_t* s_vieww = lds_at<uint64_t>(smem, L.view);
+  uint64_t* s_key = lds_at<uint64_t>(smem, L.key);
+  uint64_t* s_affw = lds_at<uint64_t>(smem, L.aff);
+  uint64_t* s_misc = lds_at<uint64_t>(smem, L.misc);
+  uint32_t* s_ver = lds_at<uint32_t>(smem, L.ver);
+  uint32_t* s_node = lds_at<uint32_t>(smem, L.node);
+  int32_t* s_c = lds_at<int32_t>(smem, L.c);
+  uint32_t* bitmap = lds_at<uint32_t>(smem, L.bitmap);
+  uint32_t* s_prevn = lds_at<uint32_t>(smem, L.prevn);
+  uint64_t* s_pre = lds_at<uint64_t>(smem, L.pre);
+  lds_stage(s_cand, cand, 0, nb, kCandStride, tid, kNuma2Threads);
+  lds_stage(lds_at<uint64_t>(smem, L.s.pods), pods, first, nb, kPodWords, tid, kNuma2Threads);
+  lds_stage(lds_at<uint64_t>(smem, L.s.npods), npods, first, nb, kNumaPodWords, tid, kNuma2Threads);
   for (int w = tid; w < bitmap_words; w += kNuma2Threads) bitmap[w] = 0;
   if (tid < kWave) s_ver[tid] = 0;
   if (tid < 16) s_c[tid] = 0;
@@ -2258,13 +2190,13 @@ __global__ __launch_bounds__(kNuma2Threads) void resolve_round_numa2(DevTable T,
     *em = NT.m[m];
     *reinterpret_cast<NumaView*>(e + kRowWords + kNumaStaticWords + kNumaMutWords) = make_view(es, em, NP);
   }
-  const DevPod* s_pods = reinterpret_cast<const DevPod*>(s_podw);
-  const NumaPod* s_np = reinterpret_cast<const NumaPod*>(s_npw);
-  NumaStatic* s_ns = reinterpret_cast<NumaStatic*>(s_nsw);
-  NumaMut* s_nm = reinterpret_cast<NumaMut*>(s_nmw);
-  Row* s_row = reinterpret_cast<Row*>(s_roww);
-  NumaMut* s_rnm = reinterpret_cast<NumaMut*>(s_rnmw);
-  NumaView* s_view = reinterpret_cast<NumaView*>(s_vieww);
+  const DevPod* s_pods = lds_at<const DevPod>(smem, L.s.pods);
+  const NumaPod* s_np = lds_at<const NumaPod>(smem, L.s.npods);
+  NumaStatic* s_ns = lds_at<NumaStatic>(smem, L.s.ns);
+  NumaMut* s_nm = lds_at<NumaMut>(smem, L.s.nm);
+  Row* s_row = lds_at<Row>(smem, L.row);
+  NumaMut* s_rnm = lds_at<NumaMut>(smem, L.rnm);
+  NumaView* s_view = lds_at<NumaView>(smem, L.view);
   // the rows the n_prev earlier rounds modified, de-duplicated into slots [0, nM) by wave 0 (as resolve_round_numa)
   {
     const int n = gather_prev_lists(modlists, slot, depth, n_prev, s_prevn, lane, wave == 0);
@@ -2742,8 +2674,6 @@ __global__ __launch_bounds__(kWave* kEvalWaves) void eval_round_ds(const int64_t
 
 // Single-wave FIFO resolver of a DeviceShare round.  Lane l < nM owns modified node l: its Row in registers and
 // its DsNode in LDS, plus the round-start copies of both (what the wide passes saw).
-constexpr int kDsNodeWords = (int)(sizeof(DsNode) / 8), kDsPodWords = (int)(sizeof(DsPod) / 8);
-
 __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT, const DevPod* __restrict__ pods,
                                                            const DsPod* __restrict__ dpods,
                                                            int64_t* __restrict__ ctl, int64_t end, int B,
@@ -2763,23 +2693,19 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
   int nb;
   if (!ds_round_range(ctl, end, B, first, nb)) return;
   const uint64_t t_active = __builtin_amdgcn_s_memrealtime();  // the period decomposition's resolver time
-  uint64_t* s_cand = smem;                                  // [nb][kCandStride]
-  uint64_t* s_podw = s_cand + (size_t)nb * kCandStride;     // [nb] DevPod
-  uint64_t* s_dpw = s_podw + (size_t)nb * kPodWords;        // [nb] DsPod
-  uint64_t* s_cur = s_dpw + (size_t)nb * kDsPodWords;       // [kWave] DsNode, current
-  uint64_t* s_stg = s_cur + (size_t)kWave * kDsNodeWords;   // [nb] DsNode of each pod's top candidate
-  QuotaRow* s_q = reinterpret_cast<QuotaRow*>(s_stg + (size_t)nb * kDsNodeWords);  // [nq] quota rows
-  int64_t* s_qdev = reinterpret_cast<int64_t*>(s_q + nq);   // [nb][kQuotaRes] device quota requests
-  Row* s_srow = reinterpret_cast<Row*>(s_qdev + (size_t)nb * kQuotaRes);  // [nb] its Row
-  DsNode* s_d0 = reinterpret_cast<DsNode*>(s_srow + nb);    // sharded: [kWave] round-start DsNode per modified lane
-  Row* s_r0 = reinterpret_cast<Row*>(s_d0 + (sharded ? kWave : 0));  // sharded: [kWave] round-start Row
-  uint32_t* bitmap = reinterpret_cast<uint32_t*>(s_r0 + (sharded ? kWave : 0));
-  for (int w = lane; w < nb * kCandStride; w += kWave) s_cand[w] = cand[w];
+  const DsLds L = ds_lds(nb, nq, sharded != 0, bitmap_words);
+  uint64_t* s_cand = lds_at<uint64_t>(smem, L.cand);
+  DsNode* s_stg = lds_at<DsNode>(smem, L.stg);
+  QuotaRow* s_q = lds_at<QuotaRow>(smem, L.q);
+  int64_t* s_qdev = lds_at<int64_t>(smem, L.qdev);
+  Row* s_srow = lds_at<Row>(smem, L.srow);
+  DsNode* s_d0 = lds_at<DsNode>(smem, L.d0);
+  Row* s_r0 = lds_at<Row>(smem, L.r0);
+  uint32_t* bitmap = lds_at<uint32_t>(smem, L.bitmap);
+  lds_stage(s_cand, cand, 0, nb, kCandStride, lane, kWave);
   {
-    const uint64_t* pw = reinterpret_cast<const uint64_t*>(pods + first);
-    for (int w = lane; w < nb * kPodWords; w += kWave) s_podw[w] = pw[w];
-    const uint64_t* dw = reinterpret_cast<const uint64_t*>(dpods + first);
-    for (int w = lane; w < nb * kDsPodWords; w += kWave) s_dpw[w] = dw[w];
+    lds_stage(lds_at<uint64_t>(smem, L.pods), pods, first, nb, kPodWords, lane, kWave);
+    lds_stage(lds_at<uint64_t>(smem, L.dpods), dpods, first, nb, kDsPodWords, lane, kWave);
     if (nq > 0) {  // ElasticQuota rows (cpu, memory, device resources) + the pods' device requests
       const uint64_t* qw = reinterpret_cast<const uint64_t*>(quotas);
       uint64_t* sq = reinterpret_cast<uint64_t*>(s_q);
@@ -2797,13 +2723,13 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
     if (k0 != 0) {
       stg_node = key_node(k0);
       s_srow[lane] = load_row(T, stg_node);
-      __builtin_memcpy(reinterpret_cast<DsNode*>(s_stg) + lane, DT.d + stg_node, sizeof(DsNode));
+      __builtin_memcpy(s_stg + lane, DT.d + stg_node, sizeof(DsNode));
     }
   }
   __syncthreads();
-  const DevPod* s_pods = reinterpret_cast<const DevPod*>(s_podw);
-  const DsPod* s_dp = reinterpret_cast<const DsPod*>(s_dpw);
-  DsNode* s_dc = reinterpret_cast<DsNode*>(s_cur);
+  const DevPod* s_pods = lds_at<const DevPod>(smem, L.pods);
+  const DsPod* s_dp = lds_at<const DsPod>(smem, L.dpods);
+  DsNode* s_dc = lds_at<DsNode>(smem, L.cur);
   uint32_t midx = 0xFFFFFFFFu;
   Row mrow;
   mrow.flags = 0;
@@ -2884,7 +2810,7 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
       const int src = sh ? (int)__builtin_ctzll(sh) : -1;
       if (lane == owner) {  // copy the row straight into the lane's LDS slots (memcpy: alias-safe, no private copy)
         midx = w;
-        const DsNode* from = src >= 0 ? reinterpret_cast<const DsNode*>(s_stg) + src : DT.d + w;
+        const DsNode* from = src >= 0 ? s_stg + src : DT.d + w;
         mrow = src >= 0 ? s_srow[src] : load_row(T, w);
         __builtin_memcpy(&s_dc[owner], from, sizeof(DsNode));
         if (sharded) {
@@ -4032,7 +3958,7 @@ int validate_config(const kg_config* c) {
       if (c->ds_scoring_weights[r] < 0 || c->ds_scoring_weights[r] > 1000000) return fail(KG_E_INVALID, "DeviceShare scoring weight");
     if (c->ds_score && !c->ds_filter)
       return fail(KG_E_UNSUPPORTED, "DeviceShare at Score needs DeviceShare at Filter (Score errors on unfiltered nodes)");
-    if (c->batch_pods > 32) return fail(KG_E_UNSUPPORTED, "DeviceShare profiles: batch_pods <= 32");
+    if (c->batch_pods > kMaxDsB) return fail(KG_E_UNSUPPORTED, "DeviceShare profiles: batch_pods <= %d", kMaxDsB);
     if (100 * ((c->fit_score ? c->weight_fit : 0) + (c->la_score ? c->weight_loadaware : 0)) >= (1 << 23))
       return fail(KG_E_UNSUPPORTED, "DeviceShare profiles: Fit + LoadAware weights must keep totals below 2^23");
   }
@@ -4774,18 +4700,8 @@ RoundGeom geometry(const kg_engine* e) {
   return g;
 }
 
-size_t resolve_lds_bytes(const RoundGeom& g, int nb) {
-  return ((size_t)nb * (kCandStride + kPodWords) + kParWords) * 8 + (size_t)(kModHash + kMaxMod) * 4 +
-         (size_t)g.bitmap_words * 4;
-}
-constexpr size_t kMaxLds = 160 * 1024;
-size_t resolve_numa_lds_bytes(const RoundGeom& g, int nb) {
-  return ((size_t)nb * (kCandStride + kPodWords + kNumaPodWords) + (size_t)kWave * (kNumaStaticWords + kNumaMutWords)) * 8 +
-         (size_t)kWave * 4 + (size_t)g.bitmap_words * 4;
-}
 NumaTable numa_table(kg_engine* e) { return NumaTable{e->numa_s.p, e->numa_m.p}; }
 
-size_t eval_lds_bytes(const RoundGeom& g) { return (size_t)kEW * std::max(g.ppw * kR, kC) * 8; }
 // eval_round's 1-D grid: tile groups of kEW tiles × pod groups, swizzled over XCDs inside the kernel
 dim3 eval_grid_e(const RoundGeom& g, int nb) {
   return dim3((unsigned)(((g.nte + kEW - 1) / kEW) * ((nb + g.ppw - 1) / g.ppw)));
@@ -4841,7 +4757,7 @@ uint32_t* tickets_slot(kg_engine* e, int slot) { return e->tickets.p + (size_t)s
 template <int X>
 void launch_eval_round(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int slot, hipStream_t st, bool fuse) {
   auto go = [&](auto kern) {
-    kern<<<eval_grid_e(g, nb), kWave * kEW, eval_lds_bytes(g), st>>>(e->T, e->pods.p, first, nb, g.ppw, g.base,
+    kern<<<eval_grid_e(g, nb), kWave * kEW, eval_lds_bytes(kEW, g.ppw), st>>>(e->T, e->pods.p, first, nb, g.ppw, g.base,
                                                                     g.n_local, g.nte, e->P, lists_slot(e, g, slot),
                                                                     poison_ptr(e), e->paux.p,
                                                                     eval_combine(g) ? 1 : 0,
@@ -4946,33 +4862,28 @@ void launch_resolve(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int
   // wait outlasted its spin limit in r6 (test_c4_pipelined_parity[8-4], test_numa_ranks); the one-wave kernel is the
   // measured-safe choice there
   static const bool numa_one_wave = std::getenv("KG_NUMA_RESOLVER") && std::getenv("KG_NUMA_RESOLVER")[0] == '1';
-  const size_t lds2 = resolve_numa_lds_bytes(g, nb) + numa2_extra_lds_bytes();
-  if (e->numa_on && !numa_one_wave && e->n_ranks == 1 && g.depth <= 3 && lds2 <= kMaxLds) {
-    const bool pre = lds2 + numa2_pre_lds_bytes(nb) <= kMaxLds;
-    resolve_round_numa2<<<1, kNuma2Threads, lds2 + (pre ? numa2_pre_lds_bytes(nb) : 0), st>>>(
+  if (e->numa_on && !numa_one_wave && e->n_ranks == 1 && g.depth <= 3 &&
+      numa2_lds(nb, g.bitmap_words, 0).bytes() <= kMaxLds) {
+    const int npre = numa2_lds(nb, g.bitmap_words, kNumaPre).bytes() <= kMaxLds ? kNumaPre : 0;
+    resolve_round_numa2<<<1, kNuma2Threads, numa2_lds(nb, g.bitmap_words, npre).bytes(), st>>>(
         e->T, numa_table(e), e->pods.p, e->npods.p, e->cursor.p, first, nb, cand_slot(e, g, slot), e->P, e->NP,
         e->out_keys.p, e->out_cpus.p, e->out_nrec.p, g.bitmap_words, poison_ptr(e), seq, e->quotas.p, e->nq,
-        e->modlists.p, slot, g.depth, n_prev, wait, pre ? kNumaPre : 0);
+        e->modlists.p, slot, g.depth, n_prev, wait, npre);
   } else if (e->numa_on) {
-    resolve_round_numa<<<1, kWave, resolve_numa_lds_bytes(g, nb), st>>>(e->T, numa_table(e), e->pods.p, e->npods.p,
-                                                                        e->cursor.p, first, nb, cand_slot(e, g, slot),
-                                                                        e->P, e->NP, e->out_keys.p, e->out_cpus.p,
-                                                                        e->out_nrec.p,
-                                                                        g.bitmap_words, poison_ptr(e), seq, e->quotas.p,
-                                                                        e->nq, e->modlists.p, slot, g.depth, n_prev,
-                                                                        wait);
+    resolve_round_numa<<<1, kWave, numa_lds(nb, g.bitmap_words).bytes(), st>>>(
+        e->T, numa_table(e), e->pods.p, e->npods.p, e->cursor.p, first, nb, cand_slot(e, g, slot), e->P, e->NP,
+        e->out_keys.p, e->out_cpus.p, e->out_nrec.p, g.bitmap_words, poison_ptr(e), seq, e->quotas.p, e->nq,
+        e->modlists.p, slot, g.depth, n_prev, wait);
     return;
   }
 #define KG_RESOLVE_T(X, Q)                                                                                       \
-  resolve_round<X, Q><<<1, kWave, resolve_lds_bytes(g, nb), st>>>(e->T, e->pods.p, e->cursor.p, first, nb,           \
-                                                                  cand_slot(e, g, slot), e->P, e->out_keys.p,       \
-                                                                  g.bitmap_words, e->modlists.p, slot, g.depth,     \
-                                                                  n_prev, poison_ptr(e), seq, wait, e->quotas.p,    \
-                                                                  e->nq, e->paux.p)
+  resolve_round<X, Q><<<1, kWave, resolve_lds(nb, g.bitmap_words).bytes(), st>>>(                                \
+      e->T, e->pods.p, e->cursor.p, first, nb, cand_slot(e, g, slot), e->P, e->out_keys.p, g.bitmap_words,       \
+      e->modlists.p, slot, g.depth, n_prev, poison_ptr(e), seq, wait, e->quotas.p, e->nq, e->paux.p)
 #define KG_RESOLVE(X) KG_RESOLVE_T(X, false)
 #define KG_RESOLVE_Q(X) KG_RESOLVE_T(X, true)
 #define KG_RESOLVE_MW_T(X, Q)                                                                                   \
-  resolve_mw<X, Q><<<1, kMwThreads, mw_lds_bytes(nb), st>>>(e->T, e->pods.p, e->cursor.p, first, nb,              \
+  resolve_mw<X, Q><<<1, kMwThreads, mw_lds(nb).bytes(), st>>>(e->T, e->pods.p, e->cursor.p, first, nb,            \
                                                             cand_slot(e, g, slot), e->P, e->out_keys.p,         \
                                                             e->modlists.p, slot, g.depth, n_prev, poison_ptr(e), \
                                                             seq, wait, e->quotas.p, e->nq, e->paux.p)
@@ -5108,12 +5019,6 @@ int run_batch(kg_engine* e, const RoundGeom& g, int64_t cur, int64_t end, int64_
 }
 
 // ---- DeviceShare rounds: cursor-driven, unpipelined, all on rs[0] ----
-size_t resolve_ds_lds_bytes(const RoundGeom& g, int nb, int nq, bool sharded) {
-  return ((size_t)nb * (kCandStride + kPodWords + kDsPodWords + kDsNodeWords + kQuotaRes) + (size_t)kWave * kDsNodeWords) * 8 +
-         (size_t)nq * sizeof(QuotaRow) + (size_t)nb * sizeof(Row) +
-         (sharded ? (size_t)kWave * (sizeof(DsNode) + sizeof(Row)) : 0) + (size_t)g.bitmap_words * 4;
-}
-
 int launch_round_ds(kg_engine* e, const RoundGeom& g, int64_t end, hipStream_t st, int which = -1) {
   const DsTable DT{e->ds_d.p};
   const bool sharded = e->n_ranks > 1;
@@ -5152,13 +5057,11 @@ int launch_round_ds(kg_engine* e, const RoundGeom& g, int64_t end, hipStream_t s
   }
   if (which < 0 || which == 2) {
     t = prof_begin(e, st);
-    resolve_round_ds<<<1, kWave, resolve_ds_lds_bytes(g, g.B, e->nq, sharded), st>>>(e->T, DT, e->pods.p, e->dpods.p,
-                                                                            e->cursor.p, end, g.B, cand_slot(e, g, 0),
-                                                                            e->dsnorm.p, e->dsval.p,
-                                                                            (int64_t)g.nt_local * kTile, e->P, e->DP,
-                                                                            e->out_keys.p, e->out_minors.p,
-                                                                            g.bitmap_words, e->quotas.p, e->nq,
-                                                                            e->qdev.p, (int)sharded);
+    // the layout of a full round: the kernel's own nb ≤ g.B (it reads the cursor) only shortens the per-pod sections
+    resolve_round_ds<<<1, kWave, ds_lds(g.B, e->nq, sharded, g.bitmap_words).bytes(), st>>>(
+        e->T, DT, e->pods.p, e->dpods.p, e->cursor.p, end, g.B, cand_slot(e, g, 0), e->dsnorm.p, e->dsval.p,
+        (int64_t)g.nt_local * kTile, e->P, e->DP, e->out_keys.p, e->out_minors.p, g.bitmap_words, e->quotas.p, e->nq,
+        e->qdev.p, (int)sharded);
     prof_end(e, KG_PROF_RESOLVE, t, st);
   }
   return 0;
@@ -5184,14 +5087,14 @@ int prepare_rounds(kg_engine* e, RoundGeom& g) {
   if (eval_lists(e, g) > (block_merge ? kMergeThreads * kMergeChunks : 8 * kWave))
     return fail(KG_E_UNSUPPORTED, "%lld nodes per rank exceed one merge %s (%d lists per pod)", (long long)g.shard,
                 block_merge ? "block" : "wavefront", block_merge ? kMergeThreads * kMergeChunks : 8 * kWave);
-  if (e->ds_on && resolve_ds_lds_bytes(g, g.B, e->nq, e->n_ranks > 1) > kMaxLds)
-    return fail(KG_E_UNSUPPORTED, "DeviceShare resolver LDS %zu B > %zu B: fewer nodes or a smaller batch_pods",
-                resolve_ds_lds_bytes(g, g.B, e->nq, e->n_ranks > 1), kMaxLds);
-  if (!e->numa_on && !e->ds_on && resolve_lds_bytes(g, g.B) > kMaxLds)
-    return fail(KG_E_UNSUPPORTED, "resolver LDS %zu B > %zu B: fewer nodes or a smaller batch_pods",
-                resolve_lds_bytes(g, g.B), kMaxLds);
-  if (!e->numa_on && !e->ds_on && !resolver_one_wave() && mw_lds_bytes(g.B) > kMaxLds)
-    return fail(KG_E_UNSUPPORTED, "resolver LDS %zu B > %zu B: a smaller batch_pods", mw_lds_bytes(g.B), kMaxLds);
+  // the LDS of a full round of the resolver these rounds launch (the two-wave NUMA resolver only runs where it fits)
+  const size_t lds = e->ds_on               ? ds_lds(g.B, e->nq, e->n_ranks > 1, g.bitmap_words).bytes()
+                     : e->numa_on           ? numa_lds(g.B, g.bitmap_words).bytes()
+                     : !resolver_one_wave() ? mw_lds(g.B).bytes()
+                                            : resolve_lds(g.B, g.bitmap_words).bytes();
+  if (lds > kMaxLds)
+    return fail(KG_E_UNSUPPORTED, "%sresolver LDS %zu B > %zu B: fewer nodes or a smaller batch_pods",
+                e->ds_on ? "DeviceShare " : e->numa_on ? "NodeNUMAResource " : "", lds, kMaxLds);
   const size_t D = (size_t)g.depth;
   const size_t lists_n = e->lists.n;
   if (int rc = e->lists.ensure(D * g.B * g.nl_max * kR)) return rc;
@@ -5402,8 +5305,8 @@ int run_xr(kg_engine* e, int64_t first, int64_t count, kg_stats* stats, double t
   const int vbits = e->P.score_bits + 1;
   const int bitmap_words = (int)((n + 31) / 32);
   const int xf = (X.ns ? XF_NUMA : 0) | (X.ds ? XF_DS : 0) | (X.defp ? XF_DEF : 0);
-  const size_t lds = xr_resolve_lds_bytes(xf, X.nq, X.paux != nullptr, bitmap_words);
-  if (lds > 160 * 1024) return fail(KG_E_UNSUPPORTED, "exact rounds: %zu B of LDS for %lld nodes", lds, (long long)n);
+  const size_t lds = xr_lds(xf, X.nq, X.paux != nullptr, bitmap_words).bytes();
+  if (lds > kMaxLds) return fail(KG_E_UNSUPPORTED, "exact rounds: %zu B of LDS for %lld nodes", lds, (long long)n);
   const int32_t* poison = reinterpret_cast<const int32_t*>(e->rsv_ws.p + WS_ZERO);
   uint64_t* val = e->xr_val.p;
   uint32_t* val2 = e->def_score ? e->xr_val2.p : nullptr;
@@ -5912,7 +5815,7 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
       return bail(fail(KG_E_DEVICE, "hipMemset"));
     hipError_t fe = hipSuccess;
 #define KG_XR_ATTR(XF) \
-  fe = hipFuncSetAttribute((const void*)xr_resolve<XF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
+  fe = hipFuncSetAttribute((const void*)xr_resolve<XF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds)
     for (int xf = 0; xf < 8 && fe == hipSuccess; ++xf) KG_XF_SWITCH(xf, KG_XR_ATTR);
 #undef KG_XR_ATTR
     if (fe != hipSuccess) return bail(fail(KG_E_DEVICE, "hipFuncSetAttribute(xr_resolve LDS)"));
@@ -5944,11 +5847,8 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
     for (auto& d : e->ds_host) d.first = -1;
     if (hipMemcpyAsync(e->ds_d.p, e->ds_host.data(), cap * sizeof(DsNode), hipMemcpyHostToDevice, e->stream) != hipSuccess)
       return bail(fail(KG_E_DEVICE, "hipMemcpy"));
-    const int lds = (int)(kMaxNodes / 8 + ((size_t)32 * (kCandStride + kPodWords + kDsPodWords + kDsNodeWords + kQuotaRes) +
-                                           (size_t)kWave * kDsNodeWords) * 8 + KG_MAX_QUOTAS * sizeof(QuotaRow) +
-                          32 * sizeof(Row) + (size_t)kWave * (sizeof(DsNode) + sizeof(Row)));
-    const int lds_cap = (int)std::min<size_t>((size_t)lds, 160 * 1024);  // prepare_rounds checks the real need
-    if (hipFuncSetAttribute((const void*)resolve_round_ds, hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap) != hipSuccess)
+    // the attribute caps what a launch may ask for; prepare_rounds checks the real need
+    if (hipFuncSetAttribute((const void*)resolve_round_ds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds) != hipSuccess)
       return bail(fail(KG_E_DEVICE, "hipFuncSetAttribute(resolve_round_ds LDS)"));
   }
   e->NP.filter = (int32_t)(c.numa_filter != 0);
@@ -5968,11 +5868,9 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
     if (hipMemsetAsync(e->numa_s.p, 0, cap * sizeof(NumaStatic), e->stream) != hipSuccess ||
         hipMemsetAsync(e->numa_m.p, 0, cap * sizeof(NumaMut), e->stream) != hipSuccess)
       return bail(fail(KG_E_DEVICE, "hipMemset"));
-    const int lds = (int)(kMaxNodes / 8 + ((size_t)kMaxB * (kCandStride + kPodWords + kNumaPodWords) +
-                                           (size_t)kWave * (kNumaStaticWords + kNumaMutWords)) * 8);
-    if (hipFuncSetAttribute((const void*)resolve_round_numa, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)resolve_round_numa2, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)std::min<size_t>(lds + numa2_extra_lds_bytes() + numa2_pre_lds_bytes(kMaxB), kMaxLds)) !=
+    if (hipFuncSetAttribute((const void*)resolve_round_numa, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds) !=
+            hipSuccess ||
+        hipFuncSetAttribute((const void*)resolve_round_numa2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds) !=
             hipSuccess)
       return bail(fail(KG_E_DEVICE, "hipFuncSetAttribute(resolve_round_numa LDS)"));
   }

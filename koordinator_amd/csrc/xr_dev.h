@@ -24,12 +24,9 @@
 // winner and every modified row is a listed candidate).  The table and the resolver stay replicated.
 #pragma once
 
-constexpr int kXrPods = 32;      // pods per round (< kWave: one modified row per resolver lane)
+// kXrPods (pods per round), the XF_* feature bits and xr_resolve's LDS layout (xr_lds) are in round_lds.h
 constexpr int kXrPpw = 2;        // pods per select wave (4 x 2 = 8 waves per tile group: enough waves to fill the chip)
 constexpr int kXrNorm = 5;       // per-pod statistics: preferred key, raw Reservation, DeviceShare, taint, affinity
-// Exact-round features (compile-time: the kernels carry only the plugins the profile enables, so the Fit /
-// LoadAware / Reservation-only variants keep their registers, and none spills for code it never runs)
-constexpr int XF_NUMA = 1, XF_DS = 2, XF_DEF = 4;
 static_assert(kXrPods < kWave, "resolver lanes");
 
 __device__ __forceinline__ bool xr_range(const unsigned long long* __restrict__ ws, int64_t& first, int& nb) {
@@ -298,19 +295,6 @@ __global__ __launch_bounds__(kWave* kEvalWaves) void xr_select(const uint64_t* _
   }
 }
 
-constexpr int kRsvPodWords = (int)(sizeof(RsvPod) / 8), kDefPodWords = (int)((sizeof(DefPod) + 7) / 8);
-
-// LDS bytes of xr_resolve: the records, the pods' staged per-plugin records, the quota rows, the modified bitmap
-__host__ __device__ inline size_t xr_resolve_lds_bytes(int XF, int nq, bool aux, int bitmap_words) {
-  size_t w = (size_t)kXrPods * (kC + 1) + (size_t)kXrPods * (kPodWords + kRsvPodWords);
-  if (XF & XF_DS) w += (size_t)kXrPods * kDsPodWords;
-  if (XF & XF_NUMA) w += (size_t)kXrPods * kNumaPodWords;
-  if (XF & XF_DEF) w += (size_t)kXrPods * kDefPodWords;
-  if (aux) w += (size_t)kXrPods * kAux;
-  if (nq > 0) w += (size_t)nq * (sizeof(QuotaRow) / 8) + (size_t)kXrPods * kQuotaRes;
-  return w * 8 + (size_t)bitmap_words * 4;
-}
-
 // Wave-cooperative Reserve of pod j on its winner row w (every lane calls it with the same w, v, j; `owner` holds row
 // w): NodeNUMAResource Reserve on copies (owner lane), then DeviceShare's minor choice with one lane per minor —
 // score and fit of minor m on lane m, the (score desc, minor asc) rank from the other lanes, the first `count` fitting
@@ -448,32 +432,23 @@ __global__ __launch_bounds__(kWave) void xr_resolve(DevTable T, RsvNode* __restr
   const int lane = threadIdx.x;
   const int nq = X.nq;
   const bool has_aux = X.paux != nullptr;
-  uint64_t* s_cand = smem;                                        // [kXrPods][kC + 1]
-  uint64_t* s_podw = s_cand + (size_t)kXrPods * (kC + 1);         // [kXrPods][kPodWords]
-  uint64_t* s_rpw = s_podw + (size_t)kXrPods * kPodWords;         // [kXrPods][kRsvPodWords]
-  uint64_t* s_next = s_rpw + (size_t)kXrPods * kRsvPodWords;
-  uint64_t* s_dpw = s_next;                                        // [kXrPods][kDsPodWords]      (DS)
-  if (kDs) s_next += (size_t)kXrPods * kDsPodWords;
-  uint64_t* s_npw = s_next;                                        // [kXrPods][kNumaPodWords]    (NUMA)
-  if (kNuma) s_next += (size_t)kXrPods * kNumaPodWords;
-  uint64_t* s_dfw = s_next;                                        // [kXrPods][kDefPodWords]     (defaults)
-  if (kDef) s_next += (size_t)kXrPods * kDefPodWords;
-  int64_t* s_aux = reinterpret_cast<int64_t*>(s_next);             // [kXrPods][kAux]             (aux requests)
-  if (has_aux) s_next += (size_t)kXrPods * kAux;
-  QuotaRow* s_q = reinterpret_cast<QuotaRow*>(s_next);             // [nq]
-  int64_t* s_qdev = reinterpret_cast<int64_t*>(s_q + nq);          // [kXrPods][kQuotaRes]
-  if (nq > 0) s_next += (size_t)nq * (sizeof(QuotaRow) / 8) + (size_t)kXrPods * kQuotaRes;
-  uint32_t* bitmap = reinterpret_cast<uint32_t*>(s_next);
+  const XrLds L = xr_lds(XF, nq, has_aux, bitmap_words);
+  uint64_t* s_cand = lds_at<uint64_t>(smem, L.cand);
+  uint64_t* s_podw = lds_at<uint64_t>(smem, L.pods);
+  uint64_t* s_rpw = lds_at<uint64_t>(smem, L.rpods);
+  uint64_t* s_dpw = lds_at<uint64_t>(smem, L.dpods);
+  uint64_t* s_npw = lds_at<uint64_t>(smem, L.npods);
+  uint64_t* s_dfw = lds_at<uint64_t>(smem, L.defp);
+  int64_t* s_aux = lds_at<int64_t>(smem, L.aux);
+  QuotaRow* s_q = lds_at<QuotaRow>(smem, L.q);
+  int64_t* s_qdev = lds_at<int64_t>(smem, L.qdev);
+  uint32_t* bitmap = lds_at<uint32_t>(smem, L.bitmap);
   {  // one bulk load of everything the per-pod chain reads
     for (int w = lane; w < nb * (kC + 1); w += kWave) s_cand[w] = cand[(size_t)(w / (kC + 1)) * kCandStride + w % (kC + 1)];
-    auto stage = [&](uint64_t* dst, const void* src, int words) {
-      const uint64_t* g = reinterpret_cast<const uint64_t*>(src);
-      for (int w = lane; w < nb * words; w += kWave) dst[w] = g[(size_t)first * words + w];
-    };
-    stage(s_podw, pods, kPodWords);
-    stage(s_rpw, rpods, kRsvPodWords);
-    if (kDs) stage(s_dpw, X.dpods, kDsPodWords);
-    if (kNuma) stage(s_npw, X.npods, kNumaPodWords);
+    lds_stage(s_podw, pods, first, nb, kPodWords, lane, kWave);
+    lds_stage(s_rpw, rpods, first, nb, kRsvPodWords, lane, kWave);
+    if (kDs) lds_stage(s_dpw, X.dpods, first, nb, kDsPodWords, lane, kWave);
+    if (kNuma) lds_stage(s_npw, X.npods, first, nb, kNumaPodWords, lane, kWave);
     if (kDef) {  // DefPod (sizeof: 184 B since ABI 10): byte-exact copy of the nb records
       const uint32_t* g = reinterpret_cast<const uint32_t*>(X.defp + first);
       uint32_t* d = reinterpret_cast<uint32_t*>(s_dfw);
