@@ -123,7 +123,8 @@ typedef const __attribute__((address_space(1))) void* global_cvoid_ptr;
 // ---- round kernel 1: wide evaluation -------------------------------------------------------------
 // One wave = one tile of kTile nodes (lane l holds nodes tile*kTile + j*64 + l, j < kNPT, as HotRows in
 // registers) × pods_per_wave pods of the round [first, first + nb).  Writes lists[(pod, tile)][kR] = the
-// tile's top-kR packed keys (ascending node order, zero-padded).  The table may be mid-update by the previous
+// tile's top-kR packed keys (ascending node order, zero-padded), or on a shard of kCombineTiles tiles or more
+// lists[(pod, tile group)][kRG] = the group's top-kRG keys (descending).  The table may be mid-update by the previous
 // round's resolver (pipelining): every column load is a single aligned 8-/4-byte load, so a
 // row reads as a mix of pre- and post-assume columns, whose key is ≥ the row's current key (monotone profile);
 // the resolver re-scores those rows exactly.  `poison` ≠ 0: an earlier round of this batch stopped early, so
@@ -204,14 +205,141 @@ __device__ __forceinline__ void select_write(const uint32_t (&v)[NPT], const uin
   if (lane >= base && lane < kR) out[lane] = 0;
 }
 
+// What eval_tile does with one pod's values of the wave's tile (pl = the pod's index in the block's pod group).
+// TileListSink: the tile's top-kR keys into the pod's list (a shard under kCombineTiles tiles, and the tile-select +
+// combine path of a pod group too large to stage).
+struct TileListSink {
+  uint64_t* out;
+  int64_t stride;
+  int vbits;
+  template <int NPT>
+  __device__ __forceinline__ void operator()(int pl, const uint32_t (&v)[NPT], const uint32_t (&gidx)[NPT],
+                                             int lane) const {
+    select_write(v, gidx, vbits, out + (size_t)pl * stride, lane);
+  }
+};
+// TileStageSink: the values themselves into the block's LDS, [pod][tile][lane][j] (one 8-byte store per lane at
+// NPT = 2: consecutive lanes, consecutive banks); no select runs in the pod loop, the block selects once per (pod, tile
+// group) after its barrier (group_select_write).  vals = this wave's tile of pod 0.
+struct TileStageSink {
+  uint32_t* vals;
+  int pod_stride;
+  template <int NPT>
+  __device__ __forceinline__ void operator()(int pl, const uint32_t (&v)[NPT], const uint32_t (&)[NPT], int lane) const {
+    uint32_t* d = vals + (size_t)pl * pod_stride + lane * NPT;
+    if constexpr (NPT == 2) {
+      *reinterpret_cast<uint2*>(d) = make_uint2(v[0], v[1]);
+    } else if constexpr (NPT == 4) {
+      *reinterpret_cast<uint4*>(d) = make_uint4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < NPT; ++j) d[j] = v[j];
+    }
+  }
+};
+
+// (pod, tile group): the kRG best of the group's NV·64 values into `out`, in descending key order, zero-padded — the
+// top-kRG of the union of the tiles' top-kR lists (kRG ≤ kR), without the tile selects.  x[r] of lane l is the value
+// of node gidx0 + r·64 + l (r = tile·NPT + j: ascending node index in (r, lane) order), sel = kRG words of this
+// wave's LDS.  τ as in select_write (the window below the maximum, else the full bisection), with one cheaper step
+// first: the kRG-th largest of the 64 per-lane maxima (one ballot per step) bounds τ from below, so the 16-ballot steps
+// only bisect [that bound, maximum] — none when kRG lanes hold the maximum.  The output pass recomputes v > τ and
+// v == τ per register (no NV mask pairs stay alive) and skips a register with nothing selected on a scalar branch.
+template <int NV>
+__device__ __forceinline__ void group_select_write(const uint32_t (&x)[NV], uint32_t gidx0, int vbits, uint64_t* sel,
+                                                   uint64_t* __restrict__ out, int lane) {
+  static_assert(kRG % 2 == 0 && kRG <= kWave, "the rank pass reads key pairs, one key per lane");
+  const auto count_ge = [&](uint32_t c) {
+    int n = 0;
+#pragma unroll
+    for (int r = 0; r < NV; ++r) n += __popcll(__ballot(x[r] >= c));
+    return n;
+  };
+  uint32_t m = 0;
+#pragma unroll
+  for (int r = 0; r < NV; ++r) m = x[r] > m ? x[r] : m;
+  const uint32_t top = wave_max_u32(m);
+  // selected: x > tau, and the first `need` of x == tau in node order; tau = 0: every non-zero value, no ties
+  uint32_t tau = 0;
+  if (top != 0) {
+    constexpr uint32_t kSelWin = 16;
+    const uint32_t lo = top > kSelWin ? top - (kSelWin - 1) : 1u;
+    uint32_t cur = 0;
+    if (__popcll(__ballot(m >= lo)) >= kRG) {  // count(x ≥ c) ≥ count(m ≥ c)
+      cur = lo;
+#pragma unroll
+      for (int b = 3; b >= 0; --b) {
+        const uint32_t c = cur + (1u << b);
+        if (c <= top && __popcll(__ballot(m >= c)) >= kRG) cur = c;
+      }
+    } else if (count_ge(lo) >= kRG) {
+      cur = lo;
+    }
+    if (cur != 0) {  // τ ∈ [cur, top], top − cur < kSelWin
+      const uint32_t d = top - cur;
+      for (int b = d ? 31 - __clz((int)d) : -1; b >= 0; --b) {
+        const uint32_t c = cur + (1u << b);
+        if (c <= top && count_ge(c) >= kRG) cur = c;
+      }
+      tau = cur;
+    } else if (count_ge(1u) > kRG) {
+      for (int b = vbits - 1; b >= 0; --b) {
+        const uint32_t c = cur | (1u << b);
+        if (count_ge(c) >= kRG) cur = c;
+      }
+      tau = cur;
+    }
+  }
+  int need = 0;
+  if (tau != 0) {
+    need = kRG;
+#pragma unroll
+    for (int r = 0; r < NV; ++r) need -= __popcll(__ballot(x[r] > tau));
+  }
+  // the selected keys to sel[0, n) in node order (ties at τ by a masked bit count, as in select_write) ...
+  const uint64_t lane_lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  int n = 0, eqbase = 0;
+#pragma unroll
+  for (int r = 0; r < NV; ++r) {
+    const uint64_t gt = __ballot(x[r] > tau);
+    uint64_t eq = 0;
+    if (eqbase < need) eq = __ballot(x[r] == tau);
+    if ((gt | eq) == 0) continue;  // wave-uniform
+    const bool pick = ((gt >> lane) & 1ull) || (((eq >> lane) & 1ull) && eqbase + __popcll(eq & lane_lt) < need);
+    const uint64_t s = __ballot(pick);
+    if (pick) sel[n + __popcll(s & lane_lt)] = make_key(x[r] - 1, gidx0 + (uint32_t)(r * kWave + lane));
+    n += __popcll(s);
+    eqbase += __popcll(eq);
+  }
+  if (lane >= n && lane < kRG) sel[lane] = 0;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  // ... and out by rank: the ≤ kRG keys are unique, position = number of larger keys (score descending, then node
+  // index ascending)
+  if (lane < kRG) {
+    const uint64_t key = sel[lane];
+    int rank = 0;
+    const ulonglong2* s2 = reinterpret_cast<const ulonglong2*>(sel);
+#pragma unroll
+    for (int q = 0; q < kRG / 2; ++q) {
+      const ulonglong2 y = s2[q];  // broadcast LDS reads
+      rank += (y.x > key) + (y.y > key);
+    }
+    out[key != 0 ? rank : lane] = key;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();  // sel is the next pod's too
+}
+
 // A tile holding a row outside eval_hot's exact domain: the reference-shaped int64 path for every pod (rare).
 // The row index is laundered inside the loop so the compiler cannot hoist the 19 column addresses out of it
 // (they would stay live across the wide loop and halve its occupancy).
-template <int NPT>
+template <int NPT, class Sink>
 __device__ __forceinline__ void eval_tile_exact(const DevTable& T, const DevPod* __restrict__ pods, int64_t first,
                                              int p0, int p1, int tile, int64_t node_base, int64_t n_local,
-                                             const EvalParams& P, uint64_t* __restrict__ out, int64_t out_stride,
-                                             int vbits, const int64_t* __restrict__ paux) {
+                                             const EvalParams& P, const Sink& sink,
+                                             const int64_t* __restrict__ paux) {
   const int lane = threadIdx.x % kWave;
   uint32_t gidx[NPT];
 #pragma unroll
@@ -228,16 +356,15 @@ __device__ __forceinline__ void eval_tile_exact(const DevTable& T, const DevPod*
       if (P.fit_filter && (p.flags & P_AUX) && v[j] && !aux_fits(T, node_base + local, paux + (size_t)(first + pi) * kAux))
         v[j] = 0;
     }
-    select_write(v, gidx, vbits, out + (size_t)(pi - p0) * out_stride, lane);
+    sink(pi - p0, v, gidx, lane);
   }
 }
 
-// one wave's tile for pods [p0, p1): its kR best packed keys per pod into out[(pi - p0) * kR ..]
-template <int PF, int NPT, bool AUX>
+// one wave's tile for pods [p0, p1): each pod's values v[j] = feasible ? total + 1 : 0 go to the sink
+template <int PF, int NPT, bool AUX, class Sink>
 __device__ __forceinline__ void eval_tile(const DevTable& T, const DevPod* __restrict__ pods, int64_t first, int p0,
                                           int p1, int tile, int64_t node_base, int64_t n_local, const EvalParams& P,
-                                          uint64_t* __restrict__ out, int64_t out_stride, int vbits,
-                                          const int64_t* __restrict__ paux, int lane) {
+                                          const Sink& sink, const int64_t* __restrict__ paux, int lane) {
 
   HotRow rows[NPT];
   uint32_t gidx[NPT];
@@ -267,7 +394,7 @@ __device__ __forceinline__ void eval_tile(const DevTable& T, const DevPod* __res
   KG_STAMP(0, 1);
   // a row outside eval_hot's exact domain anywhere in the tile: the whole tile takes the exact path
   if (__ballot(rare)) {
-    eval_tile_exact<NPT>(T, pods, first, p0, p1, tile, node_base, n_local, P, out, out_stride, vbits, paux);
+    eval_tile_exact<NPT>(T, pods, first, p0, p1, tile, node_base, n_local, P, sink, paux);
     return;
   }
   for (int pi = p0; pi < p1; ++pi) {
@@ -288,7 +415,7 @@ __device__ __forceinline__ void eval_tile(const DevTable& T, const DevPod* __res
           if (v[j] && !aux_fits(T, gidx[j], rq)) v[j] = 0;
       }
     }
-    select_write(v, gidx, vbits, out + (size_t)(pi - p0) * out_stride, lane);
+    sink(pi - p0, v, gidx, lane);
   }
 }
 
@@ -373,45 +500,88 @@ __global__ __launch_bounds__(kWave* kEW) KG_EVAL_ATTR void eval_round(DevTable T
   if (tile0 >= nt_local || p0 >= nb) return;  // block-uniform
   const int p1 = (p0 + pods_per_wave) < nb ? (p0 + pods_per_wave) : nb;
   const int vbits = P.score_bits + 1;  // v = total + 1 ≤ 2^score_bits
-  // (r4) each wave's per-pod tile top-kR goes to LDS; the block then combines its kEW tiles into one
-  // top-kR list per (pod, tile group) — a quarter of the candidate lists for the merge to read and rank
-  // (a shard of fewer than kCombineTiles tiles keeps one list per tile: a pod's record needs kC candidates)
-  extern __shared__ __attribute__((aligned(16))) uint64_t s_lists[];  // [kEW][pods_per_wave][kR]
+  // Tile groups (shards of kCombineTiles tiles or more): one top-kRG list per (pod, tile group of kEW tiles) — an
+  // eighth of the candidate lists for the merge to read and rank.  Each wave stages its pods' values of its tile in LDS
+  // and the block selects once per (pod, group) after the barrier; a pod group too large to stage (eval_lds) takes
+  // the tile top-kR lists to LDS instead and combines them.  A shard of fewer than kCombineTiles tiles keeps one list
+  // per tile: a pod's record needs kC candidates.
+  extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
+  const EvalLds L = eval_lds(kEW, kETile, kRG, pods_per_wave, combine != 0);
+  uint64_t* const s_lists = lds_at<uint64_t>(smem, L.lists);  // [kEW][pods_per_wave][kR] (the tile lists to combine)
   const int ng_local = (nt_local + kEW - 1) / kEW, grp = tile0 / kEW;
   if (!combine) {
     if (tile < nt_local)
-      eval_tile<PF, kENPT, AUX>(T, pods, first, p0, p1, tile, node_base, n_local, P, lists + ((size_t)p0 * nt_local + tile) * kR,
-                    (int64_t)nt_local * kR, vbits, paux, lane);
+      eval_tile<PF, kENPT, AUX>(T, pods, first, p0, p1, tile, node_base, n_local, P,
+                                TileListSink{lists + ((size_t)p0 * nt_local + tile) * kR, (int64_t)nt_local * kR, vbits},
+                                paux, lane);
 #if KG_FUSE_TAIL
     if (tickets) merge_tail<kR>(T, P, lists, nt_local, p0, p1, pods_per_wave, ng_local, tickets, records, s_lists);
 #endif
     return;
   }
-  uint64_t* my_l = s_lists + (size_t)wave * pods_per_wave * kR;
-  if (tile < nt_local) eval_tile<PF, kENPT, AUX>(T, pods, first, p0, p1, tile, node_base, n_local, P, my_l, kR, vbits, paux, lane);
-  else
-    for (int q = lane; q < (p1 - p0) * kR; q += kWave) my_l[q] = 0;
-  __syncthreads();
-  // group list = the kR largest of the block's kEW·kR keys, in descending key order (within one score:
-  // ascending node index, as the merge's tie rule reads lists); a full group list's minimum bounds every key the
-  // block left out, as a full tile list's did (a full tile list's kR keys are all in the union)
-  static_assert(kEW * kR <= kWave, "one key per lane");
-  for (int pl = wave; pl < p1 - p0; pl += kEW) {
-    const uint64_t key = lane < kEW * kR ? s_lists[((size_t)(lane / kR) * pods_per_wave + pl) * kR + lane % kR] : 0;
-    int rank = 0;
+  if (L.staged) {
+    constexpr int kPodVals = kEW * kETile;  // [pod][tile][lane][j]
+    uint32_t* const vals = lds_at<uint32_t>(smem, L.vals);
+    uint32_t* const my_v = vals + wave * kETile;
+    if (tile < nt_local) {
+      eval_tile<PF, kENPT, AUX>(T, pods, first, p0, p1, tile, node_base, n_local, P, TileStageSink{my_v, kPodVals}, paux,
+                                lane);
+    } else {  // a tile past the shard: no node, no value
+      for (int pl = 0; pl < p1 - p0; ++pl)
 #pragma unroll
-    for (int w = 0; w < kEW; ++w) {
-      const ulonglong2* l2 = reinterpret_cast<const ulonglong2*>(s_lists + ((size_t)w * pods_per_wave + pl) * kR);
-#pragma unroll
-      for (int q = 0; q < kR / 2; ++q) {
-        const ulonglong2 x = l2[q];  // broadcast LDS reads
-        rank += (x.x > key) + (x.y > key);
-      }
+        for (int j = 0; j < kENPT; ++j) my_v[(size_t)pl * kPodVals + j * kWave + lane] = 0;
     }
-    const int nnz = __popcll(__ballot(key != 0));
-    uint64_t* out = lists + ((size_t)(p0 + pl) * ng_local + grp) * kRG;  // the kRG best (a full list still bounds)
-    if (key != 0 && rank < kRG) out[rank] = key;
-    if (lane >= nnz && lane < kRG) out[lane] = 0;
+    __syncthreads();
+    KG_STAMP(0, 2);
+    uint64_t* const my_sel = lds_at<uint64_t>(smem, L.sel) + wave * kRG;
+    for (int pl = wave; pl < p1 - p0; pl += kEW) {
+      constexpr int kNV = kEW * kENPT;
+      uint32_t x[kNV];
+      const uint32_t* src = vals + (size_t)pl * kPodVals + lane * kENPT;
+#pragma unroll
+      for (int t = 0; t < kEW; ++t) {
+        if constexpr (kENPT == 2) {
+          const uint2 v2 = *reinterpret_cast<const uint2*>(src + t * kETile);
+          x[2 * t] = v2.x;
+          x[2 * t + 1] = v2.y;
+        } else {
+#pragma unroll
+          for (int j = 0; j < kENPT; ++j) x[t * kENPT + j] = src[t * kETile + j];
+        }
+      }
+      group_select_write(x, (uint32_t)(node_base + (int64_t)tile0 * kETile), vbits, my_sel,
+                         lists + ((size_t)(p0 + pl) * ng_local + grp) * kRG, lane);
+    }
+  } else {
+    uint64_t* my_l = s_lists + (size_t)wave * pods_per_wave * kR;
+    if (tile < nt_local)
+      eval_tile<PF, kENPT, AUX>(T, pods, first, p0, p1, tile, node_base, n_local, P, TileListSink{my_l, kR, vbits}, paux,
+                                lane);
+    else
+      for (int q = lane; q < (p1 - p0) * kR; q += kWave) my_l[q] = 0;
+    __syncthreads();
+    KG_STAMP(0, 2);
+    // group list = the kR largest of the block's kEW·kR keys, in descending key order (within one score:
+    // ascending node index, as the merge's tie rule reads lists); a full group list's minimum bounds every key the
+    // block left out, as a full tile list's did (a full tile list's kR keys are all in the union)
+    static_assert(kEW * kR <= kWave, "one key per lane");
+    for (int pl = wave; pl < p1 - p0; pl += kEW) {
+      const uint64_t key = lane < kEW * kR ? s_lists[((size_t)(lane / kR) * pods_per_wave + pl) * kR + lane % kR] : 0;
+      int rank = 0;
+#pragma unroll
+      for (int w = 0; w < kEW; ++w) {
+        const ulonglong2* l2 = reinterpret_cast<const ulonglong2*>(s_lists + ((size_t)w * pods_per_wave + pl) * kR);
+#pragma unroll
+        for (int q = 0; q < kR / 2; ++q) {
+          const ulonglong2 x = l2[q];  // broadcast LDS reads
+          rank += (x.x > key) + (x.y > key);
+        }
+      }
+      const int nnz = __popcll(__ballot(key != 0));
+      uint64_t* out = lists + ((size_t)(p0 + pl) * ng_local + grp) * kRG;  // the kRG best (a full list still bounds)
+      if (key != 0 && rank < kRG) out[rank] = key;
+      if (lane >= nnz && lane < kRG) out[lane] = 0;
+    }
   }
 #if KG_FUSE_TAIL
   if (tickets) merge_tail<kRG>(T, P, lists, ng_local, p0, p1, pods_per_wave, ng_local, tickets, records, s_lists);
@@ -791,10 +961,15 @@ __device__ __forceinline__ void merge_pod(const DevTable& T, const EvalParams& P
   uint32_t tau = 0, need = kC;
   if (!all) {
     // τ = the largest t with count(sc ≥ t) ≥ kC, bisected over (lo, hi]: count(sc ≥ lo) = total ≥ kC holds at lo = 1,
-    // and no key reaches the best key's score + 2
+    // and no key reaches the best key's score + 2.  The first probe is the 16-score window below the best key
+    // (select_write's window: the kC best usually lie inside it, and 4 more steps end the search); any probe inside
+    // (lo, hi) keeps the invariant, so τ is the same
+    constexpr uint32_t kWin = 16;
     uint32_t lo = 1, hi = (uint32_t)(top[0] >> 32) + 2;
+    bool window = hi - lo > kWin + 1;
     while (hi - lo > 1) {
-      const uint32_t mid = lo + (hi - lo) / 2;
+      const uint32_t mid = window ? hi - kWin : lo + (hi - lo) / 2;
+      window = false;
       uint32_t n = 0;
 #pragma unroll
       for (int i = 0; i < L; ++i)
@@ -4757,12 +4932,12 @@ uint32_t* tickets_slot(kg_engine* e, int slot) { return e->tickets.p + (size_t)s
 template <int X>
 void launch_eval_round(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int slot, hipStream_t st, bool fuse) {
   auto go = [&](auto kern) {
-    kern<<<eval_grid_e(g, nb), kWave * kEW, eval_lds_bytes(kEW, g.ppw), st>>>(e->T, e->pods.p, first, nb, g.ppw, g.base,
-                                                                    g.n_local, g.nte, e->P, lists_slot(e, g, slot),
-                                                                    poison_ptr(e), e->paux.p,
-                                                                    eval_combine(g) ? 1 : 0,
-                                                                    fuse ? tickets_slot(e, slot) : nullptr,
-                                                                    cand_slot(e, g, slot));
+    // the kernel carves its LDS with the same call (the ppw and the combine flag it is passed)
+    const uint32_t lds = eval_lds(kEW, kETile, kRG, g.ppw, eval_combine(g)).bytes();
+    kern<<<eval_grid_e(g, nb), kWave * kEW, lds, st>>>(e->T, e->pods.p, first, nb, g.ppw, g.base, g.n_local, g.nte, e->P,
+                                                      lists_slot(e, g, slot), poison_ptr(e), e->paux.p,
+                                                      eval_combine(g) ? 1 : 0, fuse ? tickets_slot(e, slot) : nullptr,
+                                                      cand_slot(e, g, slot));
   };
   if constexpr ((X & PF_FIT_FILTER) != 0) {
     if (e->aux_q) {

@@ -243,10 +243,33 @@ __host__ __device__ constexpr MwLds mw_lds(int nb) {
 }
 
 // ---- eval_round ----------------------------------------------------------------------------------------------------
-// [ew][max(ppw·kR, kC)] uint64: each of the block's ew waves parks its ppw pods' tile lists of kR keys (the stride
-// the kernel indexes with); the fused merge tail reuses the block's allocation for a pod's kC keys per wave
-__host__ __device__ constexpr uint32_t eval_lds_bytes(int ew, int ppw) {
-  return (uint32_t)ew * (uint32_t)(ppw * kR > kC ? ppw * kR : kC) * 8u;
+// A block of ew waves (tiles of tile_nodes nodes) × ppw pods.  On tile groups (`combine`) each wave stages its pods'
+// values of its tile, ew · ppw · tile_nodes uint32 as [pod][tile][lane][j] — a wave's stores and the selecting wave's
+// loads both run over consecutive lanes, so neither meets a bank conflict — and each wave has rg words for the keys it
+// selected.  4 KiB per pod at the 1,024-node group: 32 KiB at ppw = 8, two blocks per CU resident as the kernel's four
+// waves per SIMD allow.  A block whose staging would pass kEvalStageCap (ppw > 15 there) does not stage: two blocks
+// would no longer share a CU's 160 KiB, and the launch would need the large-LDS opt-in; such a pod group, and a shard without tile groups,
+// parks tile lists instead: [ew][max(ppw·kR, kC)] uint64, ppw lists of kR keys per wave (the stride the kernel indexes
+// with).  The fused merge tail reuses the start of the allocation for a pod's kC keys per wave (`lists` either way).
+constexpr uint32_t kEvalStageCap = 64 * 1024;
+struct EvalLds : LdsLayout {
+  uint32_t lists, vals, sel;
+  bool staged;  // the values are staged and selected per (pod, tile group); else tile lists (combined if `combine`)
+};
+__host__ __device__ constexpr EvalLds eval_lds(int ew, int tile_nodes, int rg, int ppw, bool combine) {
+  LdsCarver c;
+  EvalLds L{};
+  const uint32_t tail = (uint32_t)ew * kC * 2;  // the fused tail's keys, in uint32 words
+  const uint32_t vals = (uint32_t)ew * (uint32_t)ppw * (uint32_t)tile_nodes;
+  L.staged = combine && vals * 4u + (uint32_t)(ew * rg) * 8u <= kEvalStageCap;
+  if (L.staged) {
+    L.vals = L.lists = c.take<uint32_t, 16>(vals > tail ? vals : tail);  // [ppw][ew][kWave][tile_nodes / kWave]
+    L.sel = c.take<uint64_t, 16>(ew * rg);                               // [ew][rg] selected keys, before their ranking
+  } else {
+    L.lists = c.take<uint64_t, 16>(ew * (ppw * kR > kC ? ppw * kR : kC));
+  }
+  L.end = c.bytes();
+  return L;
 }
 
 // ---- the bounds at the engine's maxima -----------------------------------------------------------------------------
@@ -258,6 +281,15 @@ __host__ __device__ constexpr uint32_t eval_lds_bytes(int ew, int ppw) {
 constexpr int kMaxBitmapWords = (int)(kMaxNodes / 32);
 static_assert(resolve_lds(kMaxB, kMaxBitmapWords).bytes() <= kMaxLds, "resolve_round at kMaxB pods, kMaxNodes nodes");
 static_assert(mw_lds(kMaxB).bytes() <= kMaxLds, "resolve_mw at kMaxB pods");
+// eval_round at its shape (8 waves of 128-node tiles, 8 keys per group list): two blocks of 8 pods per wave share a CU
+// with their values staged; past kEvalStageCap a block parks tile lists, which fit the default dynamic-LDS limit at
+// any pod count
+static_assert(eval_lds(8, 128, 8, 8, true).staged && 2 * eval_lds(8, 128, 8, 8, true).bytes() <= kMaxLds,
+              "eval_round: two blocks per CU at 8 pods per wave");
+static_assert(eval_lds(8, 128, 8, 15, true).staged && eval_lds(8, 128, 8, 15, true).bytes() <= kEvalStageCap &&
+                  !eval_lds(8, 128, 8, 16, true).staged && eval_lds(8, 128, 8, kMaxB, true).bytes() <= kEvalStageCap &&
+                  eval_lds(8, 128, 8, kMaxB, false).bytes() <= kEvalStageCap,
+              "eval_round: staged up to 15 pods per wave, tile lists beyond, 64 KiB at most either way");
 static_assert(numa_lds(kMaxB, kMaxBitmapWords).bytes() <= kMaxLds, "resolve_round_numa at kMaxB pods, kMaxNodes nodes");
 static_assert(xr_lds(XF_NUMA | XF_DS | XF_DEF, KG_MAX_QUOTAS, true, kMaxBitmapWords).bytes() <= kMaxLds,
               "xr_resolve with every section at kMaxNodes nodes");
