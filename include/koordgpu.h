@@ -44,6 +44,9 @@
  *   kg_node_bound_pods_set  the bound pods preemption reads (NodeInfo.Pods), resident per node on the device;
  *                           kg_pods_preempt_resident runs the victim selection, the PDB split, the dry run and the pick
  *                           over that table: one pod record and a PDB budget vector go up per PostFilter call.
+ *   kg_nominated_pods_set   the nominator (upstream PodNominator: AddNominatedPod / DeleteNominatedPodIfExists), resident on the
+ *                           device; kg_pods_schedule_staged_nominated and the resident preemption calls then filter as
+ *                           RunFilterPluginsWithNominatedPods does (framework_extender.go:204-258 wraps it).
  *   kg_last_error           error text for the last failing call on this thread (maps to framework.NewStatus(Error,…)).
  *
  * Units follow the reference's getResourceValue (load_aware/helper.go:146-151): cpu-like resources in
@@ -1057,6 +1060,57 @@ int kg_pods_preempt_resident(kg_engine* e, const kg_pod* pod, int32_t pod_priori
                              const int32_t* node_idx /* nullable */, const int32_t* pdb_allowed, int32_t n_pdbs,
                              kg_preempt_pick* out_pick, int64_t* out_victim_uid, int32_t* out_victim_index,
                              int64_t victims_cap, int32_t* out_reject /* nullable: n_candidates words */);
+
+/* (added within ABI 18: five functions, no new struct; the ABI number is unchanged)
+ * Nominated pods, resident on the device: what PostFilter's preemption leaves behind (the preemptor is *nominated* on
+ * the picked node) and upstream's RunFilterPluginsWithNominatedPods / addNominatedPods honour until the preemptor is
+ * scheduled (k8s.io/kubernetes v1.24.15 pkg/scheduler/framework/runtime/framework.go; restated as published and NOT
+ * pinned by a reference table, like pickOneNodeForPreemption above).
+ *   - The rule.  Before pod P of PodPriority q is filtered on node n, every live table entry on n with priority >= q
+ *     (equal included) and a uid other than P's is added to the node as NodeInfo.AddPod does: Requested grows by the
+ *     entry's requests (cpu, memory, ephemeral-storage, the scalar resources) and the pod count by one, an all-zero
+ *     entry included.  Filters must pass on that node and, when anything was added, on the plain node as well.  Of the
+ *     accelerated Filters only NodeResourcesFit and NodeNUMAResource's filterAmplifiedCPUs read what AddPod changes
+ *     (NodeNUMAResource has no PreFilterExtensions; DeviceShare's AddPod returns for a pod without an allocation), and
+ *     both are monotone in Requested: the feasible set is the plain Filter AND those two on the augmented row.  Score,
+ *     NormalizeScore and the pick use the plain node, normalised over the feasible set so narrowed.
+ *   - kg_nominated_pods_set REPLACES the whole table (n = 0 empties it): the caller's nominator, re-sent after every
+ *     AddNominatedPod / DeleteNominatedPodIfExists / UpdateNominatedPod.  pods[k].uid must be non-zero and unique,
+ *     node_idx[k] a valid row, n <= KG_MAX_NOMINATED: otherwise KG_E_INVALID, naming the entry.  The requests read from
+ *     each kg_pod are the ones kg_pods_add reads; priority[k] is its PodPriority.  One upload.  KG_E_UNSUPPORTED for
+ *     n > 0, with a message saying which: a profile that enables Reservation (its AddPod moves state.preemptible), a
+ *     PodTopologySpread / InterPodAffinity profile (their AddPod moves cluster-wide counters), an engine of several ranks.
+ *     kg_nodes_delete does not touch the table: re-send it.
+ *   - kg_nominated_pods_read: the live entries from the DEVICE copy, in stored order — (node, priority descending),
+ *     ties in the caller's order — at most cap of them; *out_n = the live entries.
+ *   - kg_pods_schedule_staged_nominated is kg_pods_schedule_staged with priority[k] = the PodPriority of staged pod
+ *     first + k (kg_pod holds only the koordinator priority class).  When the engine places a pod whose uid is in the
+ *     table, that entry dies before the next pod of the queue is evaluated, whichever node the pod landed on
+ *     (upstream's assume → DeleteNominatedPodIfExists); a pod answered with -1 keeps its entry; kg_pods_unreserve does
+ *     not bring an entry back (the caller re-adds it when it re-queues the pod).  Pods no entry can affect (priority
+ *     above every live entry's, uid not in the table) take the unchanged paths; the others take the exact per-pod
+ *     pass.  Results are fetched with kg_results_fetch*.  With an empty table it is kg_pods_schedule_staged.
+ *   - While the table is non-empty, kg_pods_schedule and kg_pods_schedule_staged return KG_E_INVALID: they hold no
+ *     priorities and must not ignore the table silently.
+ *   - kg_pods_filter_nominated: for one pod, per node slot, out_reject[i] = the KG_REJECT_FIT_* / KG_REJECT_NUMA bits of
+ *     the augmented pass alone (0 = it passes; KG_REJECT_NUMA here is filterAmplifiedCPUs only; KG_REJECT_INVALID_NODE
+ *     for an invalid slot) and out_added[i] = the entries added.  The FitError of a pod blocked only by nominations.
+ *   - kg_pods_select_victims_resident / kg_pods_preempt_resident honour the table: each candidate's NodeInfo copy gets
+ *     the entries of priority >= pod_priority and a uid other than pod->uid added after its victims are removed, and
+ *     they stay added for every reprieve step (elasticquota/preempt.go:161,179 run RunFilterPluginsWithNominatedPods).
+ *     kg_pods_select_victims, kg_pods_preempt and kg_pods_filter_preemption do not read the table.
+ *   - kg_pods_evaluate*, kg_pods_diagnose and kg_debug_topn keep reporting the PLAIN Filter: with a non-empty table a
+ *     node they call feasible may be refused by kg_pods_schedule_staged_nominated (kg_pods_filter_nominated says why).
+ *   - kg_nominated_counters, since the last kg_nominated_pods_set: out[0] pods scheduled through the unchanged paths,
+ *     out[1] pods scheduled through the per-pod pass with the table, out[2] entries removed by placement. */
+#define KG_MAX_NOMINATED 4096
+int kg_nominated_pods_set(kg_engine* e, int64_t n, const kg_pod* pods, const int32_t* node_idx, const int32_t* priority);
+int kg_nominated_pods_read(kg_engine* e, int64_t cap, int64_t* out_uid, int32_t* out_node_idx, int32_t* out_priority,
+                           int64_t* out_n);
+int kg_pods_schedule_staged_nominated(kg_engine* e, int64_t first, int64_t count, const int32_t* priority,
+                                      kg_stats* stats);
+int kg_pods_filter_nominated(kg_engine* e, const kg_pod* pod, int32_t priority, int32_t* out_reject, int32_t* out_added);
+int kg_nominated_counters(kg_engine* e, int64_t* out /* 3 words */);
 
 const char* kg_last_error(void);
 int kg_abi_version(void);

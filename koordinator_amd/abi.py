@@ -236,6 +236,8 @@ PREEMPT_PICK_DTYPE = np.dtype([_i64("candidate"), _i64("node_idx"), _i64("eligib
 MAX_PDBS = 64  # KG_MAX_PDBS
 PREEMPT_RULE_QUOTA = 1  # KG_PREEMPT_RULE_QUOTA: Koordinator's canPreempt (else upstream's: lower priority only)
 ENTRY_POTENTIAL, ENTRY_VIOLATING, ENTRY_VICTIM = 1, 2, 4  # bits of select_victims_resident's per-entry byte
+# (added within ABI 18) the resident nominated-pod table: kg_nominated_pods_set
+MAX_NOMINATED = 4096  # KG_MAX_NOMINATED
 
 STRUCT_DTYPES = {0: CONFIG_DTYPE, 1: NODE_DTYPE, 2: METRIC_DTYPE, 3: POD_DTYPE, 4: STATS_DTYPE, 5: NODE_NUMA_DTYPE,
                  6: NODE_DEVICE_DTYPE, 7: QUOTA_DTYPE, 8: NODE_RSV_DTYPE, 9: POD_METRIC_DTYPE, 10: NODE_PRED_DTYPE,
@@ -261,6 +263,8 @@ EXPORTED_SYMBOLS = (
     "kg_pods_select_victims", "kg_debug_topn", "kg_pods_diagnose", "kg_pods_pick_candidate", "kg_pods_preempt",
     "kg_node_bound_pods_set", "kg_nodes_read_bound_pods", "kg_pods_select_victims_resident",
     "kg_pods_preempt_resident", "kg_debug_round_records", "kg_debug_merge",
+    "kg_nominated_pods_set", "kg_nominated_pods_read", "kg_pods_schedule_staged_nominated",
+    "kg_pods_filter_nominated", "kg_nominated_counters",
 )
 
 # int (*kg_exchange_fn)(void* user, const void* send, void* recv, int64_t bytes)
@@ -369,6 +373,11 @@ def load_library(path: str | None = None):
         "kg_pods_select_victims_resident": (i, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, i64]),
         "kg_pods_preempt_resident": (i, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, vp, i64, vp]),
         "kg_engine_create_hosted": (i, [vp, i64, i, i, EXCHANGE_FN, vp, ctypes.POINTER(vp)]),
+        "kg_nominated_pods_set": (i, [vp, i64, vp, vp, vp]),
+        "kg_nominated_pods_read": (i, [vp, i64, vp, vp, vp, vp]),
+        "kg_pods_schedule_staged_nominated": (i, [vp, i64, i64, vp, vp]),
+        "kg_pods_filter_nominated": (i, [vp, vp, i32, vp, vp]),
+        "kg_nominated_counters": (i, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL_SYMBOLS and not hasattr(lib, name):

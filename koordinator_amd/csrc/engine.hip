@@ -3166,6 +3166,13 @@ struct PreExt {
   const NodePred* __restrict__ pred;  // TaintToleration / NodeAffinity: node-static Filters
   DefParams DF;
   DefPod df;
+  // the resident entry points with a non-empty nominated-pod table (nom = nullptr otherwise): every Filter of the
+  // dry run is RunFilterPluginsWithNominatedPods (elasticquota/preempt.go:161,179), so the entries of priority >=
+  // nom_prio and another uid than nom_uid are added to the candidate's NodeInfo copy (pre_node_nominated)
+  const int32_t* __restrict__ nom;    // [cap] 1 + the node's first entry
+  NomView NV;
+  int64_t nom_uid;
+  int32_t nom_prio;
 };
 struct PreNode {
   Row r;
@@ -3270,6 +3277,22 @@ __device__ __forceinline__ void pre_node_apply(PreNode& S, const Victim& v, int6
     for (int q = 0; q < kAux; ++q) S.pre_aux[q] += sign * v.aux[q];
     S.pre_set = true;
   }
+}
+
+// addNominatedPods on the candidate's NodeInfo copy: NodeInfo.AddPod of every applicable entry (Requested of every
+// resource, NonZeroRequested is Score's and not kept, the pod count).  They are not victims: nothing enters the
+// preemptible amounts, and NodeNUMAResource / DeviceShare keep no state for a pod without an allocation.  Both Filters
+// that read the sums are monotone in Requested, so the one pass on the augmented copy decides both passes.
+__device__ __forceinline__ void pre_node_nominated(PreNode& S, const PreExt& X, int64_t i) {
+  if (!X.nom) return;
+  const int32_t f1 = X.nom[i];
+  if (!f1) return;
+  const NomSum s = nom_sum(X.NV, f1, i, X.nom_prio, X.nom_uid);
+  S.r.req_cpu += s.cpu;
+  S.r.req_mem += s.mem;
+  S.r.num_pods += s.k;
+#pragma unroll
+  for (int q = 0; q < kAux; ++q) S.aux_req[q] += s.aux[q];
 }
 
 // the pod's Filters on the candidate's current NodeInfo copy: 0 or KG_REJECT_* bits.  rq: the pod's kAux requests.
@@ -3436,6 +3459,7 @@ __global__ void select_victims(DevTable T, const RsvNode* __restrict__ RN, const
 #pragma unroll
   for (int q = 0; q < kAux; ++q) rq[q] = pod_aux[q];
   for (int64_t k = k0; k < k1; ++k) pre_node_apply(S, vic[k], 1, &X, i);
+  pre_node_nominated(S, X, i);  // after the victims are removed; they stay added for every reprieve step
   const uint32_t rej = pre_node_filter(T, S, i, p, rq, rp, P, RP, rsv_on, &X);
   out_reject[c] = (int32_t)rej;
   if (rej) return;
@@ -3947,6 +3971,23 @@ struct kg_engine {
   DevBuf<int64_t> bp_slab, bp_stage;
   DevBuf<BpDir> bp_dir;
   DevBuf<int64_t> res_buf;     // kg_pods_select_victims_resident's / kg_pods_preempt_resident's own scratch
+  // the resident nominated-pod table (kg_nominated_pods_set; nom_dev.h): the host mirror in stored order — (node,
+  // priority descending) — its arrays and the per-node first-entry column on the device, the staged pods' priority
+  // and uid for a kg_pods_schedule_staged_nominated call, and that call's state for run_rsv
+  struct NomEntry {
+    int64_t uid;
+    int32_t node, prio, live;
+    int64_t req[kNomRes];
+  };
+  std::vector<NomEntry> nom;
+  int64_t nom_live = 0;         // live entries of the mirror (> 0: the plain schedule calls are refused)
+  DevBuf<int64_t> nom_buf;      // one upload per set: uid [n], req [kNomRes][n], node / prio / live [n], first [capacity]
+  const int32_t* nom_first = nullptr;  // in nom_buf: per node 1 + its first entry, 0 = none (nullptr: empty table)
+  NomView nom_view{};
+  DevBuf<int64_t> nom_pods;     // [staged] uid, then [staged] int32 priority
+  bool nom_pass = false;        // run_rsv: evaluate with the table (X.nom)
+  int64_t nom_kill = 0;         // run_rsv: 1 + the entry of the call's last pod, 0 = none
+  int64_t nom_cnt[3] = {};      // kg_nominated_counters
   std::vector<int64_t> h_static64;
   std::vector<int32_t> h_static32;
   std::vector<double> h_static_f64;
@@ -4000,6 +4041,7 @@ struct kg_engine {
   // the instantiated reservation group graph, reused while its launch arguments are unchanged
   GraphCache rsv_exec;   // a group of kRsvGroup passes + rsv_apply
   GraphCache rsv_exec1;  // one pass + rsv_apply (single-pod calls)
+  GraphCache rsv_nexec, rsv_nexec1;  // the same two with the nominated-pod table among the arguments (nom_pass)
   DevBuf<uint64_t> rsv_part;    // [13][blocks] per-block partials (preferred-node key, max raw, max key, max ds raw,
                                 // max taint count, max affinity sum; (ABI 12) group_pre's min match / total, the
                                 // filtered-node count and the spread count / InterPodAffinity raw extremes)
@@ -5334,6 +5376,10 @@ RsvExt rsv_ext(kg_engine* e) {
   X.rpods = e->rpods.p;
   X.rsv_n = e->rsv_nd.p;
   X.rcpu = e->numa_on && e->rcpu_nodes > 0 ? e->rsv_c.p : nullptr;
+  X.nom = nullptr;  // set by run_rsv for kg_pods_schedule_staged_nominated only
+  X.NV = NomView{};
+  X.nprio = nullptr;
+  X.nuid = nullptr;
   return X;
 }
 
@@ -5367,6 +5413,13 @@ int run_rsv(kg_engine* e, int64_t first, int64_t count, kg_stats* stats, double 
     if (!e->dsx_q) X.dsx = nullptr;  // (r6) no RDMA / FPGA request staged: the lean rsv_eval variant (part of the graph key)
     const int rf = rsv_eval_flags(X);
     unsigned long long init[WS_END + 1] = {};  // the words past the call's end stay as they are
+    if (e->nom_pass) {  // kg_pods_schedule_staged_nominated: run-time pointers, part of the graph key like X.paux
+      X.nom = e->nom_first;
+      X.NV = e->nom_view;
+      X.nuid = e->nom_pods.p;
+      X.nprio = reinterpret_cast<const int32_t*>(e->nom_pods.p + e->n_staged);
+      init[WS_NOM_KILL] = (unsigned long long)e->nom_kill;
+    }
     init[WS_CURSOR] = (unsigned long long)first;
     init[WS_END] = (unsigned long long)end;
     HIP_TRY(hipMemcpyAsync(e->rsv_ws.p, init, sizeof(init), hipMemcpyHostToDevice, e->stream));
@@ -5423,7 +5476,7 @@ int run_rsv(kg_engine* e, int64_t first, int64_t count, kg_stats* stats, double 
       if (e->prof_on)
         if (int rc = prof_collect(e)) return rc;
     } else {
-      GraphCache& gc = count == 1 ? e->rsv_exec1 : e->rsv_exec;
+      GraphCache& gc = e->nom_pass ? (count == 1 ? e->rsv_nexec1 : e->rsv_nexec) : (count == 1 ? e->rsv_exec1 : e->rsv_exec);
       const int64_t per = count == 1 ? 1 : kRsvGroup;
       if (int rc = graph((int)per, gc)) return rc;
       const hipGraphExec_t ex = gc.exec;
@@ -6206,6 +6259,8 @@ void kg_engine_destroy(kg_engine* e) {
   e->rsv_val.release();
   e->rsv_exec.reset();
   e->rsv_exec1.reset();
+  e->rsv_nexec.reset();
+  e->rsv_nexec1.reset();
   e->xr_exec.reset();
   e->xr_val.release();
   e->xr_val2.release();
@@ -6237,6 +6292,8 @@ void kg_engine_destroy(kg_engine* e) {
   e->bp_stage.release();
   e->bp_dir.release();
   e->res_buf.release();
+  e->nom_buf.release();
+  e->nom_pods.release();
   e->scratch32.release();
   e->uidx.release();
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -6601,8 +6658,18 @@ static int flush_placements(kg_engine* e) {
   e->pending_place.clear();
   return 0;
 }
+// the schedule calls that carry no PodPriority must not ignore the nominated pods silently
+static int refuse_nominated(const kg_engine* e, const char* who) {
+  if (e && e->nom_live > 0)
+    return fail(KG_E_INVALID, "%s: %lld nominated pods are set and this call holds no pod priorities: use "
+                "kg_pods_schedule_staged_nominated (or empty the table with kg_nominated_pods_set(e, 0, ...))", who,
+                (long long)e->nom_live);
+  return 0;
+}
 int kg_pods_schedule_staged(kg_engine* e, int64_t first, int64_t count, kg_stats* stats) {
+  if (int rc = refuse_nominated(e, "kg_pods_schedule_staged")) return rc;
   if (int rc = schedule_staged_impl(e, first, count, stats)) return rc;
+  e->nom_cnt[0] += count;
   if (count == 0) return 0;
   // the assign time: after this call's clock (clock mode 0 keeps the newest metric time, so +1 ns = after it)
   e->pending_place.push_back({first, count, e->clock_now + (e->clock_mode == 0 ? 1 : 0)});
@@ -6754,6 +6821,7 @@ int kg_results_fetch(kg_engine* e, int64_t first, int64_t count, int32_t* out_no
 int kg_pods_schedule(kg_engine* e, const kg_pod* pods, int64_t n, int32_t* out_node, int64_t* out_score,
                      kg_stats* stats) {
   const double t0 = now_s();
+  if (int rc = refuse_nominated(e, "kg_pods_schedule")) return rc;  // before the staged queue is replaced
   if (int rc = kg_pods_stage(e, pods, n)) return rc;
   if (int rc = kg_pods_schedule_staged(e, 0, n, stats)) return rc;
   if (int rc = kg_results_fetch(e, 0, n, out_node, out_score)) return rc;
@@ -8376,6 +8444,15 @@ int kg_nodes_read_bound_pods(kg_engine* e, int32_t node_idx, int64_t* out_uid, i
   return 0;
 }
 
+// the resident dry runs see the nominated pods (a non-empty table implies a profile without Reservation)
+static void preempt_nominated(kg_engine* e, const kg_pod* pod, int32_t pod_priority, PreExt& X) {
+  if (e->nom_live == 0) return;
+  X.nom = e->nom_first;
+  X.NV = e->nom_view;
+  X.nom_uid = pod->uid;
+  X.nom_prio = pod_priority;
+}
+
 // one resident call's candidates and PDB budgets, checked against the host mirror before any launch.  entries = the
 // candidates' resident entries (the bound of the call's arrays), max_len = the longest list among them.
 static int resident_check(kg_engine* e, const char* who, int64_t n_candidates, const int32_t* node_idx,
@@ -8475,6 +8552,7 @@ int kg_pods_select_victims_resident(kg_engine* e, const kg_pod* pod, int32_t pod
   std::vector<Victim> hv;
   PreExt X;
   if (int rc = preempt_prepare(e, pod, nullptr, nullptr, nullptr, 0, lp, hv, X)) return rc;
+  preempt_nominated(e, pod, pod_priority, X);
   const size_t nc = (size_t)n_candidates, nvs = (size_t)std::max<int64_t>(entries, 1);
   Carver C;
   const ResidentLayout R = resident_layout(e, C, n_candidates, entries, true);
@@ -8533,6 +8611,7 @@ int kg_pods_preempt_resident(kg_engine* e, const kg_pod* pod, int32_t pod_priori
   std::vector<Victim> hv;
   PreExt X;
   if (int rc = preempt_prepare(e, pod, nullptr, nullptr, nullptr, 0, lp, hv, X)) return rc;
+  preempt_nominated(e, pod, pod_priority, X);
   Carver C;
   const ResidentLayout R = resident_layout(e, C, n_candidates, entries, false);
   const PickTail t = pick_tail(C, n_candidates, max_len);  // the header, then the positions
@@ -8565,6 +8644,264 @@ int kg_pods_preempt_resident(kg_engine* e, const kg_pod* pod, int32_t pod_priori
     std::memcpy(out_victim_index, hu + s_uid.words(), (size_t)h.n_victims * 4);
   }
   return 0;
+}
+
+// ---- nominated pods (nom_dev.h) ----
+
+// the table's arrays in nom_buf, for n entries and the engine's capacity
+struct NomLayout {
+  Slot<int64_t> uid, req;
+  Slot<int32_t> node, prio, live, first;
+};
+static NomLayout nom_layout(Carver& C, int64_t n, int64_t capacity) {
+  NomLayout L;
+  L.uid = C.take<int64_t>((size_t)n);
+  L.req = C.take<int64_t>((size_t)n * kNomRes);
+  L.node = C.take<int32_t>((size_t)n), L.prio = C.take<int32_t>((size_t)n), L.live = C.take<int32_t>((size_t)n);
+  L.first = C.take<int32_t>((size_t)capacity);
+  return L;
+}
+
+int kg_nominated_pods_set(kg_engine* e, int64_t n, const kg_pod* pods, const int32_t* node_idx, const int32_t* priority) {
+  if (!e || n < 0 || (n > 0 && (!pods || !node_idx || !priority))) return fail(KG_E_INVALID, "null argument");
+  if (n > KG_MAX_NOMINATED)
+    return fail(KG_E_INVALID, "kg_nominated_pods_set: %lld entries, at most %d", (long long)n, KG_MAX_NOMINATED);
+  if (n > 0) {
+    if (e->rsv_on)
+      return fail(KG_E_UNSUPPORTED, "nominated pods: a Reservation profile keeps the Go path (its AddPod moves "
+                  "state.preemptible, which a scheduling cycle then reads)");
+    if (e->grp_on)
+      return fail(KG_E_UNSUPPORTED, "nominated pods: PodTopologySpread / InterPodAffinity keep the Go path (their AddPod "
+                  "moves cluster-wide counters)");
+    if (e->n_ranks > 1)
+      return fail(KG_E_UNSUPPORTED, "nominated pods: an engine of %d ranks keeps the Go path (the table lives on one rank)",
+                  e->n_ranks);
+  }
+  std::vector<kg_engine::NomEntry> v((size_t)n);
+  {
+    std::vector<std::pair<int64_t, int64_t>> uids((size_t)n);  // (uid, entry)
+    for (int64_t k = 0; k < n; ++k) {
+      if (pods[k].uid == 0) return fail(KG_E_INVALID, "nominated pod %lld: uid 0", (long long)k);
+      const int64_t i = node_idx[k];
+      if (i < 0 || i >= e->n_nodes || !(e->nodes[i].flags & KG_NODE_VALID))
+        return fail(KG_E_INVALID, "nominated pod %lld: node index %lld is not a valid row", (long long)k, (long long)i);
+      DevPod dp;
+      if (int rc = decode_pod(e, pods[k], dp)) {
+        const std::string why = g_err;
+        return fail(rc, "nominated pod %lld: %s", (long long)k, why.c_str());
+      }
+      kg_engine::NomEntry& x = v[(size_t)k];
+      x.uid = pods[k].uid, x.node = (int32_t)i, x.prio = priority[k], x.live = 1;
+      x.req[0] = dp.req_cpu, x.req[1] = dp.req_mem;
+      for (int q = 0; q < kAux; ++q) x.req[2 + q] = pods[k].requests[kAuxFirst + q];
+      uids[(size_t)k] = {pods[k].uid, k};
+    }
+    std::sort(uids.begin(), uids.end());
+    for (int64_t k = 1; k < n; ++k)
+      if (uids[(size_t)k].first == uids[(size_t)k - 1].first)
+        return fail(KG_E_INVALID, "nominated pod %lld: uid %lld repeats entry %lld", (long long)uids[(size_t)k].second,
+                    (long long)uids[(size_t)k].first, (long long)uids[(size_t)k - 1].second);
+  }
+  std::stable_sort(v.begin(), v.end(), [](const kg_engine::NomEntry& a, const kg_engine::NomEntry& b) {
+    return a.node != b.node ? a.node < b.node : a.prio > b.prio;
+  });
+  if (n > 0) {
+    Carver C;
+    const NomLayout L = nom_layout(C, n, e->capacity);
+    std::vector<int64_t> h(C.words(), 0);
+    int64_t* b = h.data();
+    for (int64_t k = 0; k < n; ++k) {
+      const kg_engine::NomEntry& x = v[(size_t)k];
+      L.uid.at(b)[k] = x.uid;
+      for (int r = 0; r < kNomRes; ++r) L.req.at(b)[(size_t)r * n + k] = x.req[r];
+      L.node.at(b)[k] = x.node, L.prio.at(b)[k] = x.prio, L.live.at(b)[k] = 1;
+      if (k == 0 || v[(size_t)k - 1].node != x.node) L.first.at(b)[x.node] = (int32_t)k + 1;
+    }
+    if (int rc = e->nom_buf.ensure(C.words())) return rc;
+    HIP_TRY(hipMemcpyAsync(e->nom_buf.p, h.data(), C.words() * 8, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    int64_t* d = e->nom_buf.p;
+    e->nom_view = NomView{L.node.at(d), L.prio.at(d), L.uid.at(d), L.live.at(d), L.req.at(d), (int32_t)n, 0};
+    e->nom_first = L.first.at(d);
+  } else {
+    e->nom_view = NomView{};
+    e->nom_first = nullptr;
+  }
+  e->nom.swap(v);
+  e->nom_live = n;
+  e->nom_cnt[0] = e->nom_cnt[1] = e->nom_cnt[2] = 0;
+  return 0;
+}
+
+// the live flags of the device copy into the mirror; returns through `removed` how many entries died since the last look
+static int nom_refresh(kg_engine* e, int64_t& removed) {
+  removed = 0;
+  const int64_t n = (int64_t)e->nom.size();
+  if (n == 0) return 0;
+  std::vector<int32_t> live((size_t)n);
+  HIP_TRY(hipMemcpyAsync(live.data(), e->nom_view.live, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (int64_t k = 0; k < n; ++k) {
+    if (e->nom[(size_t)k].live && !live[(size_t)k]) ++removed;
+    e->nom[(size_t)k].live = live[(size_t)k] ? 1 : 0;
+  }
+  e->nom_live -= removed;
+  return 0;
+}
+
+int kg_nominated_pods_read(kg_engine* e, int64_t cap, int64_t* out_uid, int32_t* out_node_idx, int32_t* out_priority,
+                           int64_t* out_n) {
+  if (!e || !out_n || cap < 0 || (cap > 0 && (!out_uid || !out_node_idx || !out_priority)))
+    return fail(KG_E_INVALID, "null argument");
+  *out_n = 0;
+  const int64_t n = (int64_t)e->nom.size();
+  if (n == 0) return 0;
+  std::vector<int64_t> uid((size_t)n);
+  std::vector<int32_t> node((size_t)n), prio((size_t)n), live((size_t)n);
+  const NomView& V = e->nom_view;
+  HIP_TRY(hipMemcpyAsync(uid.data(), V.uid, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(node.data(), V.node, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(prio.data(), V.prio, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(live.data(), V.live, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int64_t m = 0;
+  for (int64_t k = 0; k < n; ++k) {
+    if (!live[(size_t)k]) continue;
+    if (m < cap) out_uid[m] = uid[(size_t)k], out_node_idx[m] = node[(size_t)k], out_priority[m] = prio[(size_t)k];
+    ++m;
+  }
+  *out_n = m;
+  return 0;
+}
+
+int kg_nominated_counters(kg_engine* e, int64_t* out) {
+  if (!e || !out) return fail(KG_E_INVALID, "null argument");
+  out[0] = e->nom_cnt[0], out[1] = e->nom_cnt[1], out[2] = e->nom_cnt[2];
+  return 0;
+}
+
+int kg_pods_filter_nominated(kg_engine* e, const kg_pod* pod, int32_t priority, int32_t* out_reject, int32_t* out_added) {
+  if (!e || !pod || !out_reject || !out_added) return fail(KG_E_INVALID, "null argument");
+  if (int rc = sync_static(e)) return rc;
+  LonePod lp;  // lives until the stream is synchronised
+  if (int rc = decode_lone_pod(e, *pod, 0, kLoneOptsRsvEval, lp)) return rc;
+  const int64_t n = e->n_nodes;
+  if (n == 0) return 0;
+  Carver C;
+  const auto s_pod = C.take<LonePod>(1);
+  const auto s_rej = C.take<int32_t>((size_t)n);
+  const auto s_add = C.take<int32_t>((size_t)n);
+  if (int rc = e->scratch64.ensure(C.words())) return rc;
+  int64_t* b = e->scratch64.p;
+  HIP_TRY(hipMemcpyAsync(s_pod.at(b), &lp, sizeof(lp), hipMemcpyHostToDevice, e->stream));
+  const LonePod* g = s_pod.at(b);
+  const unsigned blocks = (unsigned)((n + kNomThreads - 1) / kNomThreads);
+  nom_filter<<<blocks, kNomThreads, 0, e->stream>>>(e->T, n, &g->pod, g->aux, &g->npod,
+                                                    e->numa_on ? e->numa_s.p : nullptr, e->numa_on ? e->numa_m.p : nullptr,
+                                                    e->NP, e->P, e->nom_live > 0 ? e->nom_first : nullptr, e->nom_view,
+                                                    priority, pod->uid, s_rej.at(b), s_add.at(b));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_reject, s_rej.at(b), (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_added, s_add.at(b), (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int kg_pods_schedule_staged_nominated(kg_engine* e, int64_t first, int64_t count, const int32_t* priority,
+                                      kg_stats* stats) {
+  if (!e) return fail(KG_E_INVALID, "engine is NULL");
+  if (first < 0 || count < 0 || first + count > e->n_staged) return fail(KG_E_INVALID, "staged range");
+  if (count > 0 && !priority) return fail(KG_E_INVALID, "null argument");
+  const double t0 = now_s();
+  kg_stats total;
+  std::memset(&total, 0, sizeof(total));
+  auto add_stats = [&](const kg_stats& s) {
+    total.device_batches += s.device_batches;
+    total.node_evaluations += s.node_evaluations;
+    for (size_t k = 0; k < sizeof(total.reserved) / sizeof(total.reserved[0]); ++k) total.reserved[k] += s.reserved[k];
+  };
+  if (e->nom_live == 0) {  // an empty table: the plain call
+    if (int rc = schedule_staged_impl(e, first, count, stats)) return rc;
+    e->nom_cnt[0] += count;
+  } else if (count > 0) {
+    if (int rc = check_predicate_tables(e)) return rc;
+    // Pmax and the uids of the live entries, as of the call's start: a pod is affected when an entry can be added in
+    // front of it (priority <= Pmax) or when placing it removes one.  Entries that die during the call only make the
+    // classification conservative: the per-pod pass is exact for every pod.
+    int32_t pmax = INT32_MIN;
+    std::vector<std::pair<int64_t, int64_t>> by_uid;  // (uid, entry)
+    for (size_t k = 0; k < e->nom.size(); ++k) {
+      if (!e->nom[k].live) continue;
+      pmax = std::max(pmax, e->nom[k].prio);
+      by_uid.emplace_back(e->nom[k].uid, (int64_t)k);
+    }
+    std::sort(by_uid.begin(), by_uid.end());
+    auto entry_of = [&](int64_t uid) -> int64_t {
+      const auto it = std::lower_bound(by_uid.begin(), by_uid.end(), std::make_pair(uid, (int64_t)-1));
+      return it != by_uid.end() && it->first == uid ? it->second : -1;
+    };
+    {  // the staged pods' uid and priority, indexed by staged position
+      const size_t ns = (size_t)e->n_staged;
+      if (int rc = e->nom_pods.ensure(ns + (ns + 1) / 2)) return rc;
+      std::vector<int64_t> hu((size_t)count);
+      for (int64_t k = 0; k < count; ++k) hu[(size_t)k] = e->staged_info[(size_t)(first + k)].uid;
+      HIP_TRY(hipMemcpyAsync(e->nom_pods.p + first, hu.data(), (size_t)count * 8, hipMemcpyHostToDevice, e->stream));
+      HIP_TRY(hipMemcpyAsync(reinterpret_cast<int32_t*>(e->nom_pods.p + ns) + first, priority, (size_t)count * 4,
+                             hipMemcpyHostToDevice, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    const int64_t end = first + count;
+    int64_t a = first;
+    while (a < end) {
+      auto affected = [&](int64_t j) {
+        return priority[j - first] <= pmax || entry_of(e->staged_info[(size_t)j].uid) >= 0;
+      };
+      const bool aff = affected(a);
+      int64_t b = a + 1;
+      while (b < end && affected(b) == aff) ++b;
+      kg_stats st;
+      std::memset(&st, 0, sizeof(st));
+      if (!aff) {  // the unchanged paths: round engine, batched exact rounds or the per-pod pass, as routed today
+        if (int rc = schedule_staged_impl(e, a, b - a, &st)) return rc;
+        add_stats(st);
+        e->nom_cnt[0] += b - a;
+      } else {
+        // the per-pod pass with the table; a pass group ends after every pod that is itself nominated, so that its
+        // entry dies (rsv_apply / the call's last Reserve) before the next pod is evaluated
+        int64_t s = a;
+        while (s < b) {
+          int64_t t = s, kill = -1;
+          for (; t < b; ++t) {
+            kill = entry_of(e->staged_info[(size_t)t].uid);
+            if (kill >= 0) break;
+          }
+          const int64_t len = std::min<int64_t>(t + 1, b) - s;
+          e->nom_pass = true;
+          e->nom_kill = kill >= 0 ? kill + 1 : 0;
+          const int rc = run_rsv(e, s, len, &st, now_s());
+          e->nom_pass = false;
+          e->nom_kill = 0;
+          if (rc) return rc;
+          add_stats(st);
+          s += len;
+        }
+        e->nom_cnt[1] += b - a;
+      }
+      a = b;
+    }
+    int64_t removed = 0;
+    if (int rc = nom_refresh(e, removed)) return rc;  // the mirror follows the device
+    e->nom_cnt[2] += removed;
+    if (stats) {
+      *stats = total;
+      stats->seconds = now_s() - t0;
+    }
+  } else if (stats) {
+    std::memset(stats, 0, sizeof(*stats));
+  }
+  if (count == 0) return 0;
+  e->pending_place.push_back({first, count, e->clock_now + (e->clock_mode == 0 ? 1 : 0)});
+  return e->pm_nodes > 0 ? flush_placements(e) : 0;
 }
 
 int kg_results_fetch_reservations(kg_engine* e, int64_t first, int64_t count, int32_t* out_slot) {

@@ -293,11 +293,15 @@ __device__ __forceinline__ bool eval_node(const Row& n, const DevPod& p, const E
 
 // fitsRequest over the kAux resources for a pod requesting some of them (req: kAux values, 0 = not requested):
 // `request > Allocatable - Requested` rejects (reservation/plugin.go:469-479)
-__device__ __forceinline__ bool aux_fits(const DevTable& T, int64_t i, const int64_t* __restrict__ req) {
+// `add` (nullable, a compile-time nullptr in the scheduling passes): Requested grown by add[r], the nominated pods
+// NodeInfo.AddPod put on the row (nom_dev.h)
+__device__ __forceinline__ bool aux_fits(const DevTable& T, int64_t i, const int64_t* __restrict__ req,
+                                         const int64_t* add = nullptr) {
   bool ok = true;
 #pragma unroll
   for (int r = 0; r < kAux; ++r)
-    if (req[r] != 0) ok &= !(req[r] > T.aux[(size_t)r * T.cap + i] - T.aux[(size_t)(kAux + r) * T.cap + i]);
+    if (req[r] != 0)
+      ok &= !(req[r] > T.aux[(size_t)r * T.cap + i] - (T.aux[(size_t)(kAux + r) * T.cap + i] + (add ? add[r] : 0)));
   return ok;
 }
 

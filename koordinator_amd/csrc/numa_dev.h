@@ -979,6 +979,19 @@ __device__ __forceinline__ bool skip_the_node(const NumaPod& p, int policy) {
   return p.skip || (!p.cpu_bind && policy == 0);
 }
 
+// filterAmplifiedCPUs (plugin.go:336-373) on a node whose cpu amplification ratio is above 1: the pod's (amplified)
+// cpu request against Allocatable minus NodeInfo.Requested.MilliCPU, the cpuset part of which counts amplified.
+// node_req_cpu is the caller's Requested: the plain row's, or the row with nominated pods added (nom_dev.h).
+__device__ __forceinline__ bool numa_amp_cpu_fits(const NumaView& v, const NumaPod& p, int64_t node_req_cpu,
+                                                  int64_t node_alloc_cpu) {
+  if (p.req_cpu == 0 || !(v.amp > 1.0)) return true;
+  const int64_t pod = opt_cpu(v, p);
+  const int64_t am = v.valid ? (int64_t)v.n_alloc * 1000 : 0;  // GetAvailableCPUs needs a valid topology
+  int64_t req = node_req_cpu;
+  if (req >= am && am > 0) req = req - am + amplify(am, v.amp);
+  return !(pod > node_alloc_cpu - req);  // ErrInsufficientAmplifiedCPU
+}
+
 // NodeNUMAResource.Filter (plugin.go:276-334); writes the affinity the topology manager stores
 // `fa` / `fa_ok`: when Filter passes and has run Allocate feasibility for the affinity it stores, that
 // allocation (Score runs the same check on the same state and reuses it)
@@ -988,13 +1001,7 @@ __device__ __forceinline__ bool numa_filter(const NumaView& v, const NumaPod& p,
   fa_ok = false;
   aff = NumaHint{0, 1, 0, 0};
   if (p.prefilter_error) return false;
-  if (p.req_cpu != 0 && v.amp > 1.0) {  // filterAmplifiedCPUs (plugin.go:336-373)
-    const int64_t pod = opt_cpu(v, p);
-    const int64_t am = v.valid ? (int64_t)v.n_alloc * 1000 : 0;  // GetAvailableCPUs needs a valid topology
-    int64_t req = node_req_cpu;
-    if (req >= am && am > 0) req = req - am + amplify(am, v.amp);
-    if (pod > node_alloc_cpu - req) return false;  // ErrInsufficientAmplifiedCPU
-  }
+  if (!numa_amp_cpu_fits(v, p, node_req_cpu, node_alloc_cpu)) return false;
   if (skip_the_node(p, v.policy)) return true;
   if (p.cpu_bind) {
     if (!v.valid) return false;

@@ -31,7 +31,8 @@ static_assert(CTL_SEQ == CTL_POISON + 1 && CTL_ERROR == CTL_SEQ + 1, "poison, se
 // kg_engine::rsv_ws: the exact pass's and the exact rounds' workspace, WS_WORDS unsigned 64-bit words.
 enum WsWord : int {
   WS_QUOTA_TAG = 0,  // per-pod pass: the pod whose predecessor's quota charge rsv_select still has to write
-  WS_CURSOR = 3,     // next pod of the call (words 1 and 2 are unused)
+  WS_NOM_KILL = 1,   // per-pod pass with nominated pods: 1 + the table entry of the call's last pod, 0 = it has none
+  WS_CURSOR = 3,     // next pod of the call (word 2 is unused)
   WS_END = 4,        // the call's end (kernels launched from a graph read it here)
   WS_ROUNDS = 5,     // exact rounds run in this call
   WS_CONSUMED = 6,   // pods those rounds consumed

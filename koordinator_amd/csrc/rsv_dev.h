@@ -31,6 +31,7 @@
 #include "ds_dev.h"
 #include "groups_dev.h"
 #include "kernels.h"
+#include "nom_dev.h"
 #include "numa_dev.h"
 #include "round_ctl.h"
 
@@ -162,6 +163,12 @@ struct RsvExt {
   const int32_t* __restrict__ rsv_n;   // [cap]
   // (ABI 15) reservations holding cpusets (rcpu = nullptr: none in the cluster, or NodeNUMAResource / Reservation off)
   RsvCpu* __restrict__ rcpu;           // [cap][kRsvSlots]
+  // nominated pods (nom_dev.h; nom = nullptr: the table is empty, or the call carries no pod priorities): per node
+  // 1 + its first entry, the table, and the staged pods' PodPriority / uid.  Per-pod pass only.
+  const int32_t* __restrict__ nom;     // [cap]
+  NomView NV;
+  const int32_t* __restrict__ nprio;   // [pods]
+  const int64_t* __restrict__ nuid;    // [pods]
 };
 // pod j's zone sums (double-buffered by parity: group_pre(j) accumulates, rsv_select(j) clears j + 1's)
 __device__ __forceinline__ ZoneSums zone_sums(const RsvExt& X, int64_t j) {
@@ -664,6 +671,23 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
   return o;
 }
 
+// RunFilterPluginsWithNominatedPods' first pass for pod j on a node that holds nominated pods (f1 = X.nom[i] != 0):
+// NodeResourcesFit and filterAmplifiedCPUs on the row with the entries of priority >= the pod's added.  The plain pass
+// is rsv_eval_node's; the Scores stay the plain row's.  Nominations are refused on Reservation profiles, so the plain
+// row is the table's row (no restore).
+__device__ __forceinline__ bool rsv_nom_ok(const DevTable& T, int64_t i, int32_t f1, const DevPod& p,
+                                           const int64_t* aux_req, const EvalParams& P, const RsvExt& X, int64_t j,
+                                           const NumaPod* np) {
+  const NomSum s = nom_sum(X.NV, f1, i, X.nprio[j], X.nuid[j]);
+  if (s.k == 0) return true;
+  const Row r = load_row(T, i);
+  if (X.ns && np && X.NP.filter) {
+    const NumaView nv = make_view(X.ns + i, X.nm + i, X.NP);
+    return nom_fits(T, i, r, p, aux_req, P, s, &nv, np) == 0;
+  }
+  return nom_fits(T, i, r, p, aux_req, P, s, nullptr, nullptr) == 0;
+}
+
 // pass-1 value of a feasible node: base << 32 | dsraw << 16 | raw << 8 | feasible << 7 | (nom + 1)
 __device__ __forceinline__ uint64_t rsv_pack(const RsvOut& o) {
   return ((uint64_t)(uint32_t)o.base << 32) | ((uint64_t)(uint32_t)o.dsraw << 16) | ((uint64_t)(uint32_t)o.raw << 8) |
@@ -1016,6 +1040,7 @@ __global__ __launch_bounds__(kRsvThreads) void rsv_eval(DevTable T, RsvNode* __r
                                                                                               slot);
       out_keys[j - 1] = placed ? k : 0;
       out_slot[j - 1] = slot;
+      if (placed && X.nom && j >= end) nom_placed(X.NV, ws);  // the call's last pod: no wave evaluates a node below
       if (placed && X.nq > 0 && pods[j - 1].quota >= 0) {
         if (j >= end) rsv_quota_charge(X, pods[j - 1], j - 1);  // no later pass charges it
         else ws[WS_QUOTA_TAG] = (unsigned long long)j;                     // rsv_select(j) charges it
@@ -1084,6 +1109,11 @@ __global__ __launch_bounds__(kRsvThreads) void rsv_eval(DevTable T, RsvNode* __r
     const DefPod* df = X.defp ? &X.defp[j] : nullptr;
     RsvOut o = rsv_eval_node<true, true, (F & RSV_F_XF) != 0, (F & RSV_F_NUMA) != 0, (F & RSV_F_DS) != 0>(
         T, RN, rsv_n, i, p, rp, P, RP, X, dp, np, nullptr, aux, df);
+    // nominated pods: before rsv_pack and the block partials below, so the NormalizeScore maxima are the narrowed set's
+    if (o.feas && X.nom) {
+      const int32_t f1 = X.nom[i];
+      if (f1) o.feas = rsv_nom_ok(T, i, f1, p, aux, P, X, j, np);
+    }
     if (o.feas && X.gpods) {
       zone = X.pred[i].zone;
       o.feas = groups_filter(X.G, i, gp, X.GP, node_affinity_match(X.pred, df, i), zone, s_min, Z, pres, total);
@@ -1402,6 +1432,7 @@ __global__ __launch_bounds__(kWave) void rsv_apply(DevTable T, RsvNode* __restri
     }
     out_keys[j] = placed ? k : 0;
     out_slot[j] = slot;
+    if (placed && X.nom && j + 1 >= end) nom_placed(X.NV, ws);  // DeleteNominatedPodIfExists of the call's last pod
     if (placed) rsv_quota_charge(X, pods[j], j);
   }
   ws[WS_CURSOR] = (unsigned long long)(base + g_last + 1);

@@ -233,10 +233,16 @@ class Engine:
         return out
 
     # -- hot path -----------------------------------------------------------------------------------------
-    def schedule(self, pods: np.ndarray):
-        """Sequential FIFO scheduling with assume; returns (node_idx[-1 = unschedulable], total_score, stats)."""
+    def schedule(self, pods: np.ndarray, priorities=None):
+        """Sequential FIFO scheduling with assume; returns (node_idx[-1 = unschedulable], total_score, stats).
+        priorities (PodPriority per pod): the call honours the nominated-pod table (schedule_staged_nominated)."""
         pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
         n = len(pods)
+        if priorities is not None:
+            self.stage(pods)
+            stats = self.schedule_staged(0, n, priorities)
+            out_node, out_score = self.fetch(0, n)
+            return out_node, out_score, stats
         out_node = np.empty(n, dtype=np.int32)
         out_score = np.empty(n, dtype=np.int64)
         stats = np.zeros(1, dtype=abi.STATS_DTYPE)
@@ -247,10 +253,53 @@ class Engine:
         pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
         check(self.lib, self.lib.kg_pods_stage(self.h, ptr(pods), len(pods)))
 
-    def schedule_staged(self, first: int, count: int):
+    def schedule_staged(self, first: int, count: int, priorities=None):
+        """kg_pods_schedule_staged; with priorities (PodPriority of staged pods first .. first + count)
+        kg_pods_schedule_staged_nominated, which honours the nominated-pod table."""
         stats = np.zeros(1, dtype=abi.STATS_DTYPE)
-        check(self.lib, self.lib.kg_pods_schedule_staged(self.h, int(first), int(count), ptr(stats)))
+        if priorities is None:
+            check(self.lib, self.lib.kg_pods_schedule_staged(self.h, int(first), int(count), ptr(stats)))
+            return stats[0]
+        pr = np.ascontiguousarray(priorities, dtype=np.int32)
+        if len(pr) != count:
+            raise ValueError(f"{len(pr)} priorities for {count} pods")
+        check(self.lib, self.lib.kg_pods_schedule_staged_nominated(self.h, int(first), int(count), ptr(pr), ptr(stats)))
         return stats[0]
+
+    # -- nominated pods -----------------------------------------------------------------------------------
+    def set_nominated(self, pods, node_idx, priorities):
+        """kg_nominated_pods_set: REPLACES the nominated-pod table (empty arrays empty it)."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE).reshape(-1)
+        nodes = np.ascontiguousarray(node_idx, dtype=np.int32).reshape(-1)
+        pr = np.ascontiguousarray(priorities, dtype=np.int32).reshape(-1)
+        if not (len(pods) == len(nodes) == len(pr)):
+            raise ValueError("set_nominated: pods, node_idx and priorities differ in length")
+        check(self.lib, self.lib.kg_nominated_pods_set(self.h, len(pods), ptr(pods), ptr(nodes), ptr(pr)))
+
+    def read_nominated(self):
+        """kg_nominated_pods_read: the live entries of the DEVICE copy in stored order — (node, priority descending) —
+        as (uid int64[n], node int32[n], priority int32[n])."""
+        n = np.zeros(1, np.int64)
+        cap = abi.MAX_NOMINATED
+        uid, node, pr = np.zeros(cap, np.int64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        check(self.lib, self.lib.kg_nominated_pods_read(self.h, cap, ptr(uid), ptr(node), ptr(pr), ptr(n)))
+        k = int(n[0])
+        return uid[:k].copy(), node[:k].copy(), pr[:k].copy()
+
+    def filter_nominated(self, pod: np.ndarray, priority: int):
+        """kg_pods_filter_nominated: per node (reject bits of the pass with the nominated pods added, entries added)."""
+        pod = np.ascontiguousarray(np.asarray(pod, dtype=abi.POD_DTYPE).reshape(1))
+        n = self.num_nodes
+        rej, added = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        check(self.lib, self.lib.kg_pods_filter_nominated(self.h, ptr(pod), int(priority), ptr(rej), ptr(added)))
+        return rej[:n], added[:n]
+
+    def nominated_counters(self) -> dict:
+        """kg_nominated_counters since the last set_nominated: pods through the unchanged paths, pods through the
+        per-pod pass with the table, entries removed by placement."""
+        out = np.zeros(3, np.int64)
+        check(self.lib, self.lib.kg_nominated_counters(self.h, ptr(out)))
+        return {"plain": int(out[0]), "nominated": int(out[1]), "removed": int(out[2])}
 
     def fetch(self, first: int, count: int):
         out_node = np.empty(count, dtype=np.int32)

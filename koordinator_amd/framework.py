@@ -450,6 +450,7 @@ class Scheduler:
     def __init__(self, config: np.ndarray, capacity: int, **kw):
         self.config = config
         self.engine = Engine(config, capacity, **kw)
+        self._nominated = {}  # the nominator mirror: uid -> (pod record, PodPriority, node), in insertion order
 
     def close(self):
         self.engine.close()
@@ -508,8 +509,48 @@ class Scheduler:
         pick, uids, _idx, *rest = self.engine.preempt_resident(pod, priority, pdb_allowed, nodes, quota_rule, **kw)
         return (pick, uids, *rest)
 
-    def schedule_pods(self, pods: np.ndarray):
-        return self.engine.schedule(pods)
+    # -- the nominator (upstream's PodNominator): a mirror here, the table on the device -------------------------------
+    def _push_nominated(self):
+        ent = list(self._nominated.values())
+        pods = (np.concatenate([np.asarray(p, dtype=abi.POD_DTYPE).reshape(1) for p, _, _ in ent]) if ent
+                else np.zeros(0, dtype=abi.POD_DTYPE))
+        self.engine.set_nominated(pods, [n for _, _, n in ent], [q for _, q, _ in ent])
+
+    def add_nominated_pod(self, pod: np.ndarray, priority: int, node: int):
+        """AddNominatedPod / UpdateNominatedPod: the pod (PostFilter's preemptor) is nominated on `node`; an entry of
+        the same uid is replaced.  Every change re-sends the mirror (kg_nominated_pods_set)."""
+        rec = np.array(np.asarray(pod, dtype=abi.POD_DTYPE).reshape(1)[0])
+        uid = int(rec["uid"])
+        old = self._nominated.pop(uid, None)
+        self._nominated[uid] = (rec, int(priority), int(node))
+        try:
+            self._push_nominated()
+        except Exception:
+            del self._nominated[uid]
+            if old is not None:
+                self._nominated[uid] = old
+            raise
+
+    def delete_nominated_pod_if_exists(self, uid: int):
+        if self._nominated.pop(int(uid), None) is not None:
+            self._push_nominated()
+
+    def nominated_pods_for_node(self, node: int):
+        """NominatedPodsForNode: [(uid, PodPriority)] of the mirror's entries on `node`."""
+        return [(u, q) for u, (_, q, n) in self._nominated.items() if n == int(node)]
+
+    def _sync_nominated(self):
+        """After a schedule call: the entries the device removed (their pods were placed) leave the mirror."""
+        if self._nominated:
+            live = set(int(u) for u in self.engine.read_nominated()[0])
+            for u in [u for u in self._nominated if u not in live]:
+                del self._nominated[u]
+
+    def schedule_pods(self, pods: np.ndarray, priorities=None):
+        """FIFO scheduling of `pods`; priorities (PodPriority per pod) make the call honour the nominated pods."""
+        out = self.engine.schedule(pods, priorities)
+        self._sync_nominated()
+        return out
 
     def schedule_pod(self, pod: np.ndarray) -> ScheduleResult:
         node, score, _ = self.engine.schedule(np.asarray(pod).reshape(1))
