@@ -2,7 +2,7 @@
 // NumAllNodes, the feasible count, the NodeToStatusMap reasons histogram and the nodes per first-failing plugin
 // (Diagnosis.UnschedulablePlugins), a few hundred bytes, instead of an n-row vector per plugin copied to the host.
 //
-// Two plain launches per chunk of pods on the engine stream, in stream order (no spin on another kernel, no tickets, no
+// Two plain launches per chunk of pods on the engine stream, in stream order (no spin on another kernel, no
 // cooperative launch, no atomics on the result), over scratch of their own (the engine's diag_buf): nothing a schedule
 // call reads later is written.
 //   diag_eval    one thread per node, blocks of kRsvThreads; grid (node blocks, pod groups).  A block loops over the

@@ -419,54 +419,6 @@ __device__ __forceinline__ void eval_tile(const DevTable& T, const DevPod* __res
   }
 }
 
-template <int L, int LL>
-__device__ __forceinline__ void merge_pod(const DevTable& T, const EvalParams& P, const uint64_t* __restrict__ base,
-                                          int n_lists, uint64_t* sel, uint64_t* __restrict__ o, int lane);
-
-// (r5) The merge fused into the wide pass's tail.  Every block of a pod group publishes its lists (its stores drained,
-// the XCD L2 written back: the guide's release form) and takes a ticket; the block drawing the group's last ticket
-// acquires and merges the group's pods into their records, one pod per wave (merge_pod, as the merge_wave kernel
-// does), then resets the ticket for the slot's next round (stream order: that round's kernel starts after this one
-// ends).  n_lists ≤ 2·kWave (the caller's condition).  A round poisoned mid-launch can leave a partial count: the
-// batch is abandoned then, and every batch starts from zeroed tickets.
-template <int LL>
-__device__ __forceinline__ void merge_tail(const DevTable& T, const EvalParams& P, const uint64_t* __restrict__ lists,
-                                           int n_lists, int p0, int p1, int ppw, int n_tg, uint32_t* __restrict__ tickets,
-                                           uint64_t* __restrict__ records, uint64_t* s_lds) {
-  __shared__ uint32_t s_last;
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    uint32_t* t = tickets + p0 / ppw;
-    const uint32_t old = __hip_atomic_fetch_add(t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t last = old + 1 == (uint32_t)n_tg ? 1u : 0u;
-    if (last) {
-      __hip_atomic_store(t, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    s_last = last;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  const int64_t pstride = (int64_t)n_lists * LL;
-  uint64_t* sel = s_lds + (size_t)wave * kC;  // the block's list staging is free again: kEW·kC words (host-sized)
-  for (int pl = wave; pl < p1 - p0; pl += kEW) {
-    const uint64_t* base = lists + (size_t)(p0 + pl) * pstride;
-    uint64_t* o = records + (size_t)(p0 + pl) * kCandStride;
-    if (n_lists <= kWave) merge_pod<1, LL>(T, P, base, n_lists, sel, o, lane);
-    else merge_pod<2, LL>(T, P, base, n_lists, sel, o, lane);
-  }
-}
-
-// (r5) the fused merge tail (KG_FUSE=1 at run time) is compiled into eval_round only with -DKG_FUSE_TAIL=1: measured
-// slower (fused_merge below), and its merge code raised the wide pass's scalar-register pressure
-#ifndef KG_FUSE_TAIL
-#define KG_FUSE_TAIL 0
-#endif
 // 4 waves per SIMD for the 2-node shape: all of the C3 grid (3,136 waves) resident at once (KG_EVAL_WPE=0: the
 // compiler's choice, 130 VGPRs and 3 waves per SIMD)
 #ifndef KG_EVAL_WPE
@@ -483,9 +435,7 @@ __global__ __launch_bounds__(kWave* kEW) KG_EVAL_ATTR void eval_round(DevTable T
                                                                   int64_t node_base, int64_t n_local, int nt_local,
                                                                   EvalParams P, uint64_t* __restrict__ lists,
                                                                   const int32_t* __restrict__ poison,
-                                                                  const int64_t* __restrict__ paux, int combine,
-                                                                  uint32_t* __restrict__ tickets,
-                                                                  uint64_t* __restrict__ records) {
+                                                                  const int64_t* __restrict__ paux, int combine) {
   KG_STAMP(0, 0);
   if (*poison) return;
   const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
@@ -514,9 +464,6 @@ __global__ __launch_bounds__(kWave* kEW) KG_EVAL_ATTR void eval_round(DevTable T
       eval_tile<PF, kENPT, AUX>(T, pods, first, p0, p1, tile, node_base, n_local, P,
                                 TileListSink{lists + ((size_t)p0 * nt_local + tile) * kR, (int64_t)nt_local * kR, vbits},
                                 paux, lane);
-#if KG_FUSE_TAIL
-    if (tickets) merge_tail<kR>(T, P, lists, nt_local, p0, p1, pods_per_wave, ng_local, tickets, records, s_lists);
-#endif
     return;
   }
   if (L.staged) {
@@ -583,9 +530,6 @@ __global__ __launch_bounds__(kWave* kEW) KG_EVAL_ATTR void eval_round(DevTable T
       if (lane >= nnz && lane < kRG) out[lane] = 0;
     }
   }
-#if KG_FUSE_TAIL
-  if (tickets) merge_tail<kRG>(T, P, lists, ng_local, p0, p1, pods_per_wave, ng_local, tickets, records, s_lists);
-#endif
   KG_STAMP(0, 31);
 }
 
@@ -885,7 +829,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_round(DevTable T, EvalPar
 __device__ __forceinline__ uint32_t wave_excl_prefix_u32(uint32_t v) { return wave_prefix_sum_u32(v) - v; }
 
 // One pod's record from its n_lists candidate lists at base (list l at base + l·kR), by one wavefront; sel = kC words of
-// this wave's LDS, o = the record.  Shared by merge_wave and (r5) eval_round's fused tail (opt-in).
+// this wave's LDS, o = the record (merge_wave's body).
 // (r5) Per-step costs measured in-kernel at C3 size (KG_STAMPS, profiles/r05/stamps_merge*.txt) drove the layout: the
 // staged rows of the 3 best keys are requested first (a knock-out wave max), so their HBM latency overlaps the
 // selection instead of ending the kernel; the threshold τ is a bisection over the live score range with ballot
@@ -1476,527 +1420,6 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
   if (lane == 0) {
     ctl[CTL_SLOW] += n_slow;  // diagnostics: pods that re-scored modified rows
     round_close(ctl, poison, first, consumed, nb, t_active);
-  }
-  publish_round(ctl, seq);
-  KG_STAMP(2, 31);
-}
-
-// ---- round kernel 3 (r4): FIFO resolve with look-ahead helper waves (monotone profiles) ----------------------
-// One workgroup: the chain wave, a keeper wave and kHelpers helper waves.  resolve_round above did everything on one
-// wave, so every pod's re-score of the modified rows (~190 VALU instructions at one instruction per 4 cycles) and its
-// assume sat on the serial chain.  Here the chain only decides; the re-score moves to helpers that work kLag pods
-// ahead, and the assume to the keeper:
-//   helper(j), on the table after pods ≤ j − kLag (the winners the chain has published by then), scores pod j on
-//   every modified row (lane = slot) and on its listed candidates, and hands the chain the kTop best keys T_j of
-//   {listed candidates not modified by then} ∪ {modified rows}, each with where its row lives in LDS.
-//   chain step j: S = the winners of pods j − kLag + 1 .. j − 1 (≤ kLag − 1 nodes, the only rows that can have
-//   changed since helper(j)'s snapshot).  c* = the first entry of T_j not in S: every node outside S holds its
-//   snapshot key, and T_j is the top of those, so c* is their maximum (|S| < kTop, so some entry lies outside S).
-//   A node of S can only have lost score since the snapshot (monotone profile), so only the S nodes listed in T_j
-//   above c* need an exact re-score — on the chain's current copy of their rows.  best = max(c*, those); best < ub
-//   stops the round as before (ub bounds every node outside the pod's record, modified or not).
-// The chain publishes, per pod, the winner and its slot; the keeper applies the pod's assume to the slot's row (its
-// own register copy, lane = slot) and publishes the row's new state; each helper advances its own register copy of
-// the rows to its lag from those states, and the chain reads them only to re-score a recent winner (rare: ~5 % of C3
-// pods).
-constexpr int kMwThreads = kWave * (2 + kHelpers);  // the chain, the keeper, the helpers
-constexpr uint32_t kTopMod = 0x80000000u;  // s_topx: a modified row (its slot in the low bits); otherwise the LDS
-                                           // word offset of the candidate's round-start EvalRow
-constexpr int64_t kMwSpin = 1 << 24;       // bounded in-workgroup waits (an error instead of a hang on a bug)
-
-// Hand-offs between the resolver's waves go through LDS only, and the LDS serves one wave's DS instructions in issue
-// order: a flag written after the data it guards is seen by another wave only after that data, and that wave's data
-// reads issued after it saw the flag are served after the writes.  So publishing needs no s_waitcnt (lds_rel: a
-// compiler barrier, then the store) and observing needs none either (lds_acq: the load, then a compiler barrier) —
-// the release / acquire fences would stall the chain on its own outstanding LDS traffic for nothing.
-__device__ __forceinline__ uint32_t lds_ld(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ uint32_t lds_acq(const uint32_t* p) {
-  const uint32_t v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  asm volatile("" ::: "memory");
-  return v;
-}
-__device__ __forceinline__ void lds_rel(uint32_t* p, uint32_t v) {
-  asm volatile("" ::: "memory");
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ int mod_lookup(const uint32_t* h, uint32_t node) {
-  uint32_t i = mod_hash(node);
-  for (int it = 0; it < kModHash; ++it) {
-    const uint32_t v = lds_ld(&h[i]);
-    if (v == 0u) return -1;
-    if ((v >> 8) == node + 1u) return (int)(v & 0xFFu);
-    i = (i + 1u) & (kModHash - 1);
-  }
-  return -1;
-}
-__device__ __forceinline__ void lds_put_row(uint64_t* dst, const EvalRow& er) {
-  uint64_t w[kEvalRowWords];
-  __builtin_memcpy(w, &er, sizeof(er));
-#pragma unroll
-  for (int q = 0; q < kEvalRowWords; ++q) dst[q] = w[q];
-}
-// fitsRequest over the kAux resources on a modified row whose state includes this round's pods ≤ upto (published
-// winners in `win`)
-__device__ __forceinline__ bool mw_aux_fits(const DevTable& T, uint32_t node, const int64_t* __restrict__ rq, int upto,
-                                            const uint32_t* win, const DevPod* s_pods, const int64_t* __restrict__ prq) {
-  int64_t add[kAux] = {0, 0, 0, 0, 0};
-  for (int q = 0; q <= upto; ++q) {
-    if (lds_ld(&win[q]) != node || !(s_pods[q].flags & P_AUX)) continue;
-#pragma unroll
-    for (int r = 0; r < kAux; ++r) add[r] += prq[(size_t)q * kAux + r];
-  }
-  bool ok = true;
-#pragma unroll
-  for (int r = 0; r < kAux; ++r)
-    if (rq[r] != 0) ok &= !(rq[r] > T.aux[(size_t)r * T.cap + node] - (T.aux[(size_t)(kAux + r) * T.cap + node] + add[r]));
-  return ok;
-}
-
-template <int PF, bool QUOTA>
-__global__ __launch_bounds__(kMwThreads) void resolve_mw(DevTable T0, const DevPod* __restrict__ pods,
-                                                         int64_t* __restrict__ ctl, int64_t first, int nb,
-                                                         const uint64_t* __restrict__ cand, EvalParams P,
-                                                         uint64_t* __restrict__ out_keys,
-                                                         int32_t* __restrict__ modlists, int slot, int depth,
-                                                         int n_prev, int32_t* __restrict__ poison, int64_t seq,
-                                                         int wait, QuotaRow* __restrict__ quotas, int nq,
-                                                         const int64_t* __restrict__ paux) {
-  extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
-  KG_STAMP(2, 0);
-  const MwLds L = mw_lds(nb);
-  const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
-  if (wave == 0) __builtin_amdgcn_s_setprio(3);  // the chain first, then its helpers, then any wide-pass wave
-  else __builtin_amdgcn_s_setprio(2);
-  uint64_t* s_cand = smem + L.cand;
-  uint64_t* s_par = smem + L.par;
-  uint32_t* b32 = lds_at<uint32_t>(smem, L.u32);
-  uint32_t* s_topx = b32 + L.topx;
-  uint32_t* s_win = b32 + L.win;
-  uint32_t* s_wslot = b32 + L.wslot;
-  uint32_t* s_nsl = b32 + L.nsl;
-  uint32_t* s_ready = b32 + L.ready;
-  uint32_t* s_slot_node = b32 + L.slot_node;
-  uint32_t* s_slot_row = b32 + L.slot_row;
-  uint32_t* s_hash = b32 + L.hash;
-  uint32_t* s_prevn = b32 + L.prevn;
-  uint32_t* s_ctl = b32 + L.sctl;
-  const DevPod* s_pods = reinterpret_cast<const DevPod*>(smem + L.podw);
-  if (tid < kParWords) {
-    uint64_t pw[kParWords] = {};
-    __builtin_memcpy(pw, &P, sizeof(P));
-#pragma unroll
-    for (int q = 0; q < kParWords; ++q)
-      if (tid == q) s_par[q] = pw[q];
-  }
-  {  // prologue, independent of the previous round: LDS-DMA of the records and pods, flag / hash clears
-    const int n16 = nb * kCandStride / 2;
-    for (int it = 0; it * kMwThreads < n16; ++it) {
-      const int idx = it * kMwThreads + tid;
-      if (idx < n16)
-        __builtin_amdgcn_global_load_lds((global_cvoid_ptr)(cand + 2 * (size_t)idx),
-                                         (lds_void_ptr)(s_cand + 2 * ((size_t)it * kMwThreads + wave * kWave)), 16, 0, 0);
-    }
-    const uint64_t* pw = reinterpret_cast<const uint64_t*>(pods + first);
-    const int p16 = nb * kPodWords / 2;
-    for (int it = 0; it * kMwThreads < p16; ++it) {
-      const int idx = it * kMwThreads + tid;
-      if (idx < p16)
-        __builtin_amdgcn_global_load_lds((global_cvoid_ptr)(pw + 2 * (size_t)idx),
-                                         (lds_void_ptr)(smem + L.podw + 2 * ((size_t)it * kMwThreads + wave * kWave)), 16, 0, 0);
-    }
-    for (int w = tid; w < kModHash; w += kMwThreads) s_hash[w] = 0u;
-    for (int w = tid; w < nb; w += kMwThreads) s_ready[w] = 0u;
-    if (tid < 8) s_ctl[tid] = 0u;
-  }
-  // chain on the previous round's resolver (as resolve_round)
-  if (wave == 0) {
-    const int timed_out = __builtin_amdgcn_readfirstlane(lane == 0 ? chain_wait(ctl, seq, wait) : 0);
-    if (wait) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    KG_STAMP(2, 1);
-    // the abort is carried to the other waves in LDS and published after the barrier below, so no round_abort here
-    const int abort_ = round_stale(ctl, poison, first, timed_out);
-    if (abort_ && lane == 0 && timed_out) ctl[CTL_ERROR] = 1;
-    // rows the n_prev previous rounds modified: slots [0, nP), rows read after the chain wait
-    const int nM = abort_ ? 0 : gather_prev_lists(modlists, slot, depth, n_prev, s_prevn, lane, true);
-    __builtin_amdgcn_wave_barrier();
-    for (int s = lane; s < nM; s += kWave) {
-      const uint32_t node = s_prevn[s];
-      const bool mine = mod_insert(s_hash, node, s) == s;  // a node listed by two earlier rounds keeps its first slot
-      s_slot_node[s] = mine ? node : kNoNode;
-      s_slot_row[s] = L.prow + (uint32_t)s * kEvalRowWords;
-      if (mine) lds_put_row(smem + L.prow + (size_t)s * kEvalRowWords, make_eval_row(load_row(table_at(T0), node), P));
-    }
-    if (lane == 0) {
-      s_ctl[2] = (uint32_t)abort_;
-      s_ctl[3] = (uint32_t)nM;
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // LDS-DMA of records and pods (+ the rows above)
-  __syncthreads();
-  if (s_ctl[2]) {
-    if (wave == 0) publish_round(ctl, seq);
-    return;
-  }
-  KG_STAMP(2, 2);
-  const uint64_t t_active = __builtin_amdgcn_s_memrealtime();  // the period decomposition's resolver time
-  const int nP = (int)s_ctl[3];
-  const bool narrow = P.score_bits <= 13;  // packed keys fit 32 bits (node < 2^19 = kMaxNodes)
-  const int64_t* prq0 = paux + (size_t)first * kAux;
-
-  if (wave >= 2) {
-    // ---------------- helper waves: pods j ≡ wave − 2 (mod kHelpers) ----------------
-    // The wave keeps its own copy of the modified rows at its snapshot (lane = slot, two banks), advanced by the
-    // winners the chain publishes: a winner's row after its pod is read from s_state by its owner lane alone, so a
-    // pod costs the LDS a few single-lane row reads instead of a 64-lane one (which saturated the CU's LDS pipe).
-    int seen = nP;  // slots this wave has entered into the node → slot hash
-    int applied = -1;  // pods whose placement this wave's rows include
-    ModRow H0, H1;
-    mod_row_init(H0);
-    mod_row_init(H1);
-    if (lane < nP && s_slot_node[lane] != kNoNode) {
-      H0.node = s_slot_node[lane];
-      H0.er = lds_row(smem + L.prow + (size_t)lane * kEvalRowWords);
-    }
-    if (kWave + lane < nP && s_slot_node[kWave + lane] != kNoNode) {
-      H1.node = s_slot_node[kWave + lane];
-      H1.er = lds_row(smem + L.prow + (size_t)(kWave + lane) * kEvalRowWords);
-    }
-    for (int j = wave - 2; j < nb; j += kHelpers) {
-      const int lag = j - kLag;
-      // the snapshot needs the keeper's states of pods ≤ lag (the chain has then published them too)
-      uint32_t kept = lds_acq(&s_ctl[5]);
-      bool gone = false;
-      for (int64_t it = 0; (int)kept < lag + 1; ++it) {
-        if (lds_acq(&s_ctl[1]) && (int)lds_acq(&s_ctl[0]) < lag + 1) {  // the chain ended before pod lag
-          gone = true;
-          break;
-        }
-        if (it > kMwSpin) {
-          if (lane == 0) s_ctl[4] = 1u;  // waited too long: the round reports an error
-          gone = true;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        kept = lds_acq(&s_ctl[5]);
-      }
-      if (gone) break;
-      if (lane == 0) KG_LANE_SUB(j, 0);
-      for (int k = applied + 1; k <= lag; ++k) {  // advance the snapshot to pods ≤ lag
-        const uint32_t wk = s_win[k];
-        if (wk == kNoNode) continue;
-        const int sk = (int)s_wslot[k];
-        if (sk < kWave) {
-          if (lane == sk) H0.node = wk, H0.er = lds_row(smem + L.state + (size_t)k * kEvalRowWords);
-        } else if (lane == sk - kWave) {
-          H1.node = wk, H1.er = lds_row(smem + L.state + (size_t)k * kEvalRowWords);
-        }
-      }
-      applied = lag > applied ? lag : applied;
-      if (lane == 0) KG_LANE_SUB(j, 1);
-      const int nSl = lag >= 0 ? (int)s_nsl[lag] : nP;
-      for (int s = seen + lane; s < nSl; s += kWave) mod_insert(s_hash, s_slot_node[s], s);
-      seen = nSl > seen ? nSl : seen;
-      const DevPod p = s_pods[j];
-      const bool aux = (PF & PF_FIT_FILTER) && (p.flags & P_AUX);
-      const int64_t* rq = paux + (size_t)(first + j) * kAux;
-      // the pod's listed candidates not modified at the snapshot (in key order: lane = record position)
-      const uint64_t key = s_cand[(size_t)j * kCandStride + lane];
-      bool modl = false;
-      if (key) {
-        const int sl = mod_lookup(s_hash, key_node(key));
-        modl = sl >= 0 && sl < nSl;
-      }
-      const uint64_t um0 = __ballot(key != 0 && !modl);
-      // lane i < kTop: the i-th of them; past the record's staged rows its round-start row comes from HBM, issued
-      // now so that the load overlaps the modified rows' scoring below
-      int my_lpos = -1;
-      {
-        uint64_t u = um0;
-#pragma unroll
-        for (int i = 0; i < kTop; ++i) {
-          const int pos = u ? (int)__builtin_ctzll(u) : -1;
-          u &= u - 1;
-          if (lane == i) my_lpos = pos;
-        }
-      }
-      const uint64_t my_lkey = __shfl(key, my_lpos >= 0 ? my_lpos : 0);  // every lane takes part in the permute
-      const uint32_t my_lnode = key_node(my_lkey);
-      const bool my_hbm = my_lpos >= kStaged;
-      Row hr;
-      if (my_hbm) hr = load_row(table_at(T0), my_lnode);
-      // every modified row at the snapshot (after pods ≤ lag)
-      uint64_t mk[2] = {0, 0};
-      mk[0] = mod_row_key<PF>(H0, p, P, s_par);
-      if (aux && mk[0] && !mw_aux_fits(table_at(T0), H0.node, rq, lag, s_win, s_pods, prq0)) mk[0] = 0;
-      if (nSl > kWave) {
-        mk[1] = mod_row_key<PF>(H1, p, P, s_par);
-        if (aux && mk[1] && !mw_aux_fits(table_at(T0), H1.node, rq, lag, s_win, s_pods, prq0)) mk[1] = 0;
-      }
-      // T_j = the kTop best of the two descending sequences
-      uint64_t um = um0;
-      uint64_t tk_l = 0;
-      uint32_t tx_l = 0;
-      int n_listed = 0;  // listed entries taken so far (the n-th is lane n's my_lpos)
-      uint64_t mrest = mk[0] > mk[1] ? mk[0] : mk[1];
-      uint64_t mtop = wave_max_modkey(mrest, narrow);
-#pragma unroll
-      for (int i = 0; i < kTop; ++i) {
-        const int lpos = um ? (int)__builtin_ctzll(um) : -1;
-        const uint64_t lkey = lpos >= 0 ? readlane_u64(key, lpos) : 0;
-        uint64_t tkey;
-        uint32_t tx;
-        if (lkey == 0 && mtop == 0) {
-          tkey = 0;
-          tx = 0;
-        } else if (lkey > mtop) {
-          tkey = lkey;
-          um &= um - 1;
-          tx = lpos < kStaged ? L.cand + (uint32_t)j * kCandStride + kRecRows + (uint32_t)lpos * kEvalRowWords
-                              : L.toprow + (uint32_t)(j * kTop + n_listed) * kEvalRowWords;
-          ++n_listed;
-        } else {
-          tkey = mtop;
-          const uint64_t b0 = __ballot(mk[0] == mtop), b1 = __ballot(mk[1] == mtop);
-          const int sl = b0 ? (int)__builtin_ctzll(b0) : kWave + (int)__builtin_ctzll(b1);
-          tx = kTopMod | (uint32_t)sl;
-          if (lane == (sl & (kWave - 1))) {
-            if (sl < kWave) mk[0] = 0;
-            else mk[1] = 0;
-          }
-          mrest = mk[0] > mk[1] ? mk[0] : mk[1];
-          mtop = i + 1 < kTop ? wave_max_modkey(mrest, narrow) : 0;
-        }
-        if (lane == i) {
-          tk_l = tkey;
-          tx_l = tx;
-        }
-      }
-      if (lane == 0) KG_LANE_SUB(j, 2);
-      if (my_hbm && lane < n_listed)  // a listed entry of T_j past the staged rows: its row from the early load
-        lds_put_row(smem + L.toprow + (size_t)(j * kTop + lane) * kEvalRowWords, make_eval_row(hr, P));
-      if (lane < kTop) {
-        smem[L.top + (size_t)j * kTop + lane] = tk_l;
-        s_topx[j * kTop + lane] = tx_l;
-      }
-      if (lane == 0) lds_rel(&s_ready[j], 1u);
-      if (lane == 0) KG_LANE_SUB(j, 3);
-    }
-    return;
-  }
-
-  if (wave == 1) {
-    // ---------------- the keeper wave: the modified rows' states behind the chain ----------------
-    // For each pod the chain has published, the winner's slot takes the pod's assume (NodeInfo.AddPod + LoadAware
-    // Reserve → podAssignCache.assign) on its owner lane, and the row's new state goes to s_state[k]; helpers read
-    // their snapshots from it, the chain only when it re-scores a recent winner.
-    ModRow K0, K1;
-    mod_row_init(K0);
-    mod_row_init(K1);
-    if (lane < nP && s_slot_node[lane] != kNoNode) {
-      K0.node = s_slot_node[lane];
-      K0.er = lds_row(smem + L.prow + (size_t)lane * kEvalRowWords);
-    }
-    if (kWave + lane < nP && s_slot_node[kWave + lane] != kNoNode) {
-      K1.node = s_slot_node[kWave + lane];
-      K1.er = lds_row(smem + L.prow + (size_t)(kWave + lane) * kEvalRowWords);
-    }
-    int known = nP;  // slots this wave holds (created in order by the chain)
-    for (int k = 0; k < nb; ++k) {
-      uint32_t done = lds_acq(&s_ctl[0]);
-      for (int64_t it = 0; (int)done <= k; ++it) {
-        if (lds_acq(&s_ctl[1]) || it > kMwSpin) break;
-        __builtin_amdgcn_s_sleep(1);
-        done = lds_acq(&s_ctl[0]);
-      }
-      if ((int)done <= k) {
-        if (!lds_acq(&s_ctl[1]) && lane == 0) s_ctl[4] = 1u;
-        break;
-      }
-      const uint32_t wk = s_win[k];
-      if (wk != kNoNode) {
-        const int sk = (int)s_wslot[k];
-        const DevPod p = s_pods[k];
-        if (sk >= known) {  // a new slot: its round-start row
-          const uint32_t off = s_slot_row[sk];
-          if (sk < kWave) {
-            if (lane == sk) K0.node = wk, K0.er = lds_row(smem + off);
-          } else if (lane == sk - kWave) {
-            K1.node = wk, K1.er = lds_row(smem + off);
-          }
-          known = sk + 1;
-        }
-        if (sk < kWave) {
-          if (lane == sk) {
-            assume_mod<PF>(K0.er, p, P);
-            lds_put_row(smem + L.state + (size_t)k * kEvalRowWords, K0.er);
-          }
-        } else if (lane == sk - kWave) {
-          assume_mod<PF>(K1.er, p, P);
-          lds_put_row(smem + L.state + (size_t)k * kEvalRowWords, K1.er);
-        }
-      }
-      if (lane == 0) lds_rel(&s_ctl[5], (uint32_t)(k + 1));
-    }
-    return;
-  }
-
-  // ---------------- the chain wave ----------------
-  DevQuota ql = QUOTA ? quota_load(quotas, nq, lane) : DevQuota{0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t rw[kLag - 1];  // winners of the kLag − 1 previous pods (kNoNode: none), oldest first
-  int rsl[kLag - 1];      // their slots
-#pragma unroll
-  for (int k = 0; k < kLag - 1; ++k) rw[k] = kNoNode, rsl[k] = -1;
-  uint64_t my_out = 0;
-  int consumed = 0, n_slow = 0, n_wait = 0, nS = nP, err = 0;
-  // pod j's inputs are read during pod j − 1 (after its decision, before its publication): the helper's flag and T_j
-  // in one LDS round trip — a wave's LDS reads are served in order, so T_j read after a set flag holds what the helper
-  // wrote before it released the flag; a flag still clear is re-polled at pod j
-  uint32_t rdy_n = lds_ld(&s_ready[0]);
-  asm volatile("" ::: "memory");
-  uint64_t tk_n = lane < kTop ? smem[L.top + lane] : 0;
-  uint32_t tx_n = lane < kTop ? s_topx[lane] : 0u;
-  uint64_t ub_n = s_cand[kC];
-  DevPod p_n = s_pods[0];
-  for (int j = 0; j < nb; ++j) {
-    KG_POD_DIAG(j, (uint32_t)n_wait);
-    const uint32_t rdy = rdy_n;
-    uint64_t tk = tk_n;
-    uint32_t tx = tx_n;
-    const uint64_t ub = ub_n;
-    const DevPod p = p_n;
-    if (rdy == 0u) {
-      ++n_wait;
-      int64_t it = 0;
-      while (lds_acq(&s_ready[j]) == 0u && ++it < kMwSpin) __builtin_amdgcn_s_sleep(0);
-      if (it >= kMwSpin || lds_acq(&s_ctl[4])) {
-        err = 1;
-        break;
-      }
-      tk = lane < kTop ? smem[L.top + (size_t)j * kTop + lane] : 0;
-      tx = lane < kTop ? s_topx[j * kTop + lane] : 0u;
-    }
-    bool placed = false;
-    uint32_t w = kNoNode;
-    int wsl = -1;
-    if (!QUOTA || quota_admit(ql, p)) {  // ElasticQuota PreFilter rejects: Unschedulable, no node search
-      const uint32_t tn = key_node(tk);
-      bool inS = false;
-#pragma unroll
-      for (int k = 0; k < kLag - 1; ++k) inS |= tn == rw[k];
-      inS &= tk != 0;
-      const uint64_t okm = __ballot(tk != 0 && !inS);
-      const int pos = okm ? (int)__builtin_ctzll(okm) : kTop;
-      uint64_t best = okm ? readlane_u64(tk, pos) : 0;
-      uint64_t above = __ballot(inS && lane < pos);
-      KG_POD_SUB(j, 0);
-      bool from_s = false;
-      if (above) {  // recent winners listed above c*: re-score them exactly on their current rows (rare)
-        ++n_slow;
-        {  // the keeper has published the states of pods < j
-          int64_t it = 0;
-          while ((int)lds_acq(&s_ctl[5]) < j && ++it < kMwSpin) __builtin_amdgcn_s_sleep(0);
-          if (it >= kMwSpin) {
-            err = 1;
-            break;
-          }
-        }
-        // lane k < kLag − 1: window entry k (pod j − kLag + 1 + k); its state is the node's current row when no later
-        // entry placed the same node
-        uint32_t nd = kNoNode;
-        bool last = true;
-#pragma unroll
-        for (int k = 0; k < kLag - 1; ++k) {
-          if (lane == k) nd = rw[k];
-          if (lane < k && nd == rw[k]) last = false;
-        }
-        bool want = false;
-        while (above) {
-          const int b = (int)__builtin_ctzll(above);
-          above &= above - 1;
-          want |= nd == (uint32_t)__builtin_amdgcn_readlane((int)tn, b);
-        }
-        want &= lane < kLag - 1 && nd != kNoNode && last;
-        uint64_t mkv = 0;
-        if (want) {
-          const int step = j - (kLag - 1) + lane;
-          const EvalRow er = lds_row(smem + L.state + (size_t)step * kEvalRowWords);
-          mkv = mod_key<PF>(er, nd, p, P, s_par);
-          const bool aux = (PF & PF_FIT_FILTER) && (p.flags & P_AUX);
-          if (aux && mkv && !mod_aux_fits(table_at(T0), nd, paux + (size_t)(first + j) * kAux, j, my_out, s_pods, prq0))
-            mkv = 0;
-        }
-        const uint64_t mbest = wave_max_modkey(mkv, narrow);
-        from_s = mbest > best;
-        best = from_s ? mbest : best;
-      }
-      if (best < ub) break;  // an unseen node could still win: leave this pod to the next round
-      KG_POD_SUB(j, 1);
-      my_out = lane == j ? best : my_out;
-      if (best != 0) {  // 0: unschedulable (ub == 0: no feasible node anywhere)
-        placed = true;
-        w = key_node(best);
-        if (from_s) {  // the slot of the last window entry that placed w
-#pragma unroll
-          for (int k = 0; k < kLag - 1; ++k) wsl = rw[k] == w ? rsl[k] : wsl;
-        } else {
-          const uint32_t cx = (uint32_t)__builtin_amdgcn_readlane((int)tx, pos);
-          if (cx & kTopMod) {
-            wsl = (int)(cx & 0xFFu);
-          } else {  // a node first modified now: a new slot (the keeper loads its round-start row from LDS)
-            wsl = nS++;
-            if (lane == 0) {
-              s_slot_node[wsl] = w;
-              s_slot_row[wsl] = cx;
-            }
-          }
-        }
-      }
-    } else {
-      my_out = lane == j ? 0 : my_out;
-    }
-    KG_POD_SUB(j, 2);
-    if (QUOTA && placed) quota_charge(ql, p, lane);  // ElasticQuota Reserve
-    if (j + 1 < nb) {  // pod j + 1's inputs (see above)
-      rdy_n = lds_ld(&s_ready[j + 1]);
-      asm volatile("" ::: "memory");
-      tk_n = lane < kTop ? smem[L.top + (size_t)(j + 1) * kTop + lane] : 0;
-      tx_n = lane < kTop ? s_topx[(j + 1) * kTop + lane] : 0u;
-      ub_n = s_cand[(size_t)(j + 1) * kCandStride + kC];
-      p_n = s_pods[j + 1];
-    }
-    if (lane == 0) {
-      s_win[j] = w;
-      s_wslot[j] = (uint32_t)wsl;
-      s_nsl[j] = (uint32_t)nS;
-      lds_rel(&s_ctl[0], (uint32_t)(j + 1));
-    }
-    KG_POD_SUB(j, 3);
-    ++consumed;
-#pragma unroll
-    for (int k = 0; k + 1 < kLag - 1; ++k) rw[k] = rw[k + 1], rsl[k] = rsl[k + 1];
-    rw[kLag - 2] = w;
-    rsl[kLag - 2] = wsl;
-  }
-  if (lane == 0) lds_rel(&s_ctl[1], 1u);  // the helpers stop waiting
-  KG_STAMP(2, 30);
-  // write-back (as resolve_round): each placed pod's terms onto its winner + this round's modified-row list
-  const bool mine = !err && lane < consumed && my_out != 0;
-  const uint32_t my_node = mine ? key_node(my_out) : kNoNode;
-  if (mine) writeback_pod(table_at(T0), my_node, s_pods[lane], paux + (size_t)(first + lane) * kAux);
-  publish_mod_list(modlists, slot, mine, my_node, lane);
-  if (!err && lane < consumed) out_keys[first + lane] = my_out;
-  if (QUOTA && !err) quota_store(quotas, nq, lane, ql);
-  if (lane == 0) {
-    if (err) {
-      ctl[CTL_ERROR] = 1;  // reported as a device error by the host, which then reads no other word
-      *poison = 1;
-    } else {
-      ctl[CTL_SLOW] += n_slow;  // diagnostics: pods that re-scored recent winners on the chain
-      ctl[CTL_HELPER_WAITS] += n_wait;  // diagnostics: pods the chain waited for its helper
-      round_close(ctl, poison, first, consumed, nb, t_active);
-    }
   }
   publish_round(ctl, seq);
   KG_STAMP(2, 31);
@@ -3936,7 +3359,6 @@ struct kg_engine {
   DevBuf<uint64_t> out_keys;
   DevBuf<int64_t> cursor;     // [CTL_WORDS] the round engine's control block (round_ctl.h)
   DevBuf<int32_t> modlists;   // [kMaxDepth][kModListStride]: rows each round modified ([0] = count), by round slot
-  DevBuf<uint32_t> tickets;   // (r5) [kMaxDepth][kMaxB]: fused-merge tickets per (round slot, pod group)
   // round r runs on rs[r % D] (eval → merge → [RCCL on comms[r % D]] → resolve); `stream` runs ingest
   hipStream_t rs[kMaxDepth] = {};
   ncclComm_t comms[kMaxDepth] = {};  // comms[0] = comm; one communicator per round stream
@@ -4957,29 +4379,16 @@ uint64_t* lists_slot(kg_engine* e, const RoundGeom& g, int slot) {
 
 constexpr int kCombineTiles = 16 * kEW;  // combined lists from 16 tile groups on (128 keys ≥ kC per pod)
 bool eval_combine(const RoundGeom& g) { return g.nte >= kCombineTiles; }
-int eval_lists(kg_engine* e, const RoundGeom& g);
-uint64_t* cand_slot(kg_engine* e, const RoundGeom& g, int slot);
-bool merge_block();
-// (r5) KG_FUSE=1: the merge fused into eval_round's tail (merge_tail; one rank, the Fit + LoadAware round engine,
-// ≤ 2·kWave lists per pod, ≤ 131k nodes).  A/B option only: measured at C3 the tail merge made eval + merge 2.5 µs
-// longer than the two launches (40.8 vs 28.0 + 10.2 µs, profiles/r05/timeline_*.txt) — the boundary it removes costs
-// ~0.9 µs (scripts/micro/handoff.hip) and every block pays a release before its ticket.
-bool fused_merge(kg_engine* e, const RoundGeom& g) {
-  static const bool on = KG_FUSE_TAIL && std::getenv("KG_FUSE") && std::string(std::getenv("KG_FUSE")) == "1";
-  return on && e->n_ranks == 1 && !e->numa_on && !e->ds_on && !merge_block() && eval_lists(e, g) <= 2 * kWave;
-}
-uint32_t* tickets_slot(kg_engine* e, int slot) { return e->tickets.p + (size_t)slot * kMaxB; }
 // (r5) eval_round<PF, AUX>: the ephemeral-storage / scalar check only in the instantiation a queue with such a pod
 // runs (profiles with NodeResourcesFit's Filter)
 template <int X>
-void launch_eval_round(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int slot, hipStream_t st, bool fuse) {
+void launch_eval_round(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int slot, hipStream_t st) {
   auto go = [&](auto kern) {
     // the kernel carves its LDS with the same call (the ppw and the combine flag it is passed)
     const uint32_t lds = eval_lds(kEW, kETile, kRG, g.ppw, eval_combine(g)).bytes();
     kern<<<eval_grid_e(g, nb), kWave * kEW, lds, st>>>(e->T, e->pods.p, first, nb, g.ppw, g.base, g.n_local, g.nte, e->P,
                                                       lists_slot(e, g, slot), poison_ptr(e), e->paux.p,
-                                                      eval_combine(g) ? 1 : 0, fuse ? tickets_slot(e, slot) : nullptr,
-                                                      cand_slot(e, g, slot));
+                                                      eval_combine(g) ? 1 : 0);
   };
   if constexpr ((X & PF_FIT_FILTER) != 0) {
     if (e->aux_q) {
@@ -4990,7 +4399,7 @@ void launch_eval_round(kg_engine* e, const RoundGeom& g, int64_t first, int nb, 
   go(eval_round<X, false>);
 }
 
-void launch_eval(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int slot, hipStream_t st, bool fuse = false) {
+void launch_eval(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int slot, hipStream_t st) {
   if (e->numa_on) {  // one block per (tile, pod group)
     const dim3 grid((unsigned)(g.nt_local * ((nb + g.ppw - 1) / g.ppw)));
     eval_round_numa<<<grid, kWave * kEvalWaves, 0, st>>>(e->T, numa_table(e), e->pods.p, e->npods.p, first, nb,
@@ -4998,7 +4407,7 @@ void launch_eval(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int sl
                                                                       e->NP, lists_slot(e, g, slot), poison_ptr(e));
     return;
   }
-#define KG_EVAL(X) launch_eval_round<X>(e, g, first, nb, slot, st, fuse)
+#define KG_EVAL(X) launch_eval_round<X>(e, g, first, nb, slot, st)
   KG_PF_SWITCH(profile_bits(e->P), KG_EVAL)
 #undef KG_EVAL
 }
@@ -5014,12 +4423,6 @@ int eval_lists(kg_engine* e, const RoundGeom& g) {
 uint64_t* cand_slot(kg_engine* e, const RoundGeom& g, int slot) { return e->cand.p + (size_t)slot * g.B * kCandStride; }
 uint64_t* gathered_slot(kg_engine* e, const RoundGeom& g, int slot) {
   return e->gathered.p + (size_t)slot * e->n_ranks * g.B * kCandStride;
-}
-
-// KG_MERGE=block: the block-per-pod merge_round for eval_round's lists too (A/B measurements only)
-bool merge_block() {
-  static const bool on = std::getenv("KG_MERGE") && std::string(std::getenv("KG_MERGE")) == "block";
-  return on;
 }
 
 // One wavefront per pod: merge_wave<L, ll> for the list count, L lists per lane (nl ≤ 8·kWave, ll = kR or kRG).  The
@@ -5050,7 +4453,7 @@ void launch_merge_local(kg_engine* e, const RoundGeom& g, int nb, int slot, hipS
   // NUMA / DeviceShare passes' lists kR
   const bool grp = !e->numa_on && !e->ds_on && eval_combine(g);
   const int ll = grp ? kRG : kR;
-  if (!e->numa_on && !e->ds_on && !merge_block()) {  // (r4) one wavefront per pod
+  if (!e->numa_on && !e->ds_on) {  // (r4) one wavefront per pod
     launch_merge_wave(e->T, e->P, lists_slot(e, g, slot), nl, ll, nb, poison_ptr(e), dst, st);
     return;
   }
@@ -5064,23 +4467,14 @@ void launch_merge_ranks(kg_engine* e, const RoundGeom& g, int nb, int slot, hipS
                                                   cand_slot(e, g, slot));
 }
 
-// KG_RESOLVER=mw: the look-ahead resolve_mw (A/B measurements only).  The single-wave resolve_round is the default:
-// on MI355X at 100k nodes, depth 2, it runs the C3 queue at 869k pods/s against resolve_mw's 671k
-bool resolver_one_wave() {
-  static const bool on = !(std::getenv("KG_RESOLVER") && std::string(std::getenv("KG_RESOLVER")) == "mw");
-  return on;
-}
-
 void launch_resolve(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int slot, int n_prev,
                     int64_t seq, int wait, hipStream_t st) {
   // (r6) the two-wave resolver while the engine's round streams have hardware queues of their own (one rank, depth
-  // ≤ 3: with the main stream ≤ 4 streams, GPU_MAX_HW_QUEUES); KG_NUMA_RESOLVER=1 keeps the one-wave chain (A/B runs).
+  // ≤ 3: with the main stream ≤ 4 streams, GPU_MAX_HW_QUEUES).
   // Where streams share a queue — depth 4, or several loopback ranks in one process — the two-wave kernel's chain
   // wait outlasted its spin limit in r6 (test_c4_pipelined_parity[8-4], test_numa_ranks); the one-wave kernel is the
   // measured-safe choice there
-  static const bool numa_one_wave = std::getenv("KG_NUMA_RESOLVER") && std::getenv("KG_NUMA_RESOLVER")[0] == '1';
-  if (e->numa_on && !numa_one_wave && e->n_ranks == 1 && g.depth <= 3 &&
-      numa2_lds(nb, g.bitmap_words, 0).bytes() <= kMaxLds) {
+  if (e->numa_on && e->n_ranks == 1 && g.depth <= 3 && numa2_lds(nb, g.bitmap_words, 0).bytes() <= kMaxLds) {
     const int npre = numa2_lds(nb, g.bitmap_words, kNumaPre).bytes() <= kMaxLds ? kNumaPre : 0;
     resolve_round_numa2<<<1, kNuma2Threads, numa2_lds(nb, g.bitmap_words, npre).bytes(), st>>>(
         e->T, numa_table(e), e->pods.p, e->npods.p, e->cursor.p, first, nb, cand_slot(e, g, slot), e->P, e->NP,
@@ -5099,27 +4493,11 @@ void launch_resolve(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int
       e->modlists.p, slot, g.depth, n_prev, poison_ptr(e), seq, wait, e->quotas.p, e->nq, e->paux.p)
 #define KG_RESOLVE(X) KG_RESOLVE_T(X, false)
 #define KG_RESOLVE_Q(X) KG_RESOLVE_T(X, true)
-#define KG_RESOLVE_MW_T(X, Q)                                                                                   \
-  resolve_mw<X, Q><<<1, kMwThreads, mw_lds(nb).bytes(), st>>>(e->T, e->pods.p, e->cursor.p, first, nb,            \
-                                                            cand_slot(e, g, slot), e->P, e->out_keys.p,         \
-                                                            e->modlists.p, slot, g.depth, n_prev, poison_ptr(e), \
-                                                            seq, wait, e->quotas.p, e->nq, e->paux.p)
-#define KG_RESOLVE_MW(X) KG_RESOLVE_MW_T(X, false)
-#define KG_RESOLVE_MW_Q(X) KG_RESOLVE_MW_T(X, true)
-  if (!resolver_one_wave()) {
-    if (e->nq > 0) {
-      KG_PF_SWITCH(profile_bits(e->P), KG_RESOLVE_MW_Q)
-    } else {
-      KG_PF_SWITCH(profile_bits(e->P), KG_RESOLVE_MW)
-    }
-  } else if (e->nq > 0) {
+  if (e->nq > 0) {
     KG_PF_SWITCH(profile_bits(e->P), KG_RESOLVE_Q)
   } else {
     KG_PF_SWITCH(profile_bits(e->P), KG_RESOLVE)
   }
-#undef KG_RESOLVE_MW_Q
-#undef KG_RESOLVE_MW
-#undef KG_RESOLVE_MW_T
 #undef KG_RESOLVE_Q
 #undef KG_RESOLVE_T
 #undef KG_RESOLVE
@@ -5203,10 +4581,8 @@ int launch_merge(kg_engine* e, const RoundGeom& g, int nb, int slot, hipStream_t
 // than the early dispatch saves)
 int run_batch(kg_engine* e, const RoundGeom& g, int64_t cur, int64_t end, int64_t n_rounds) {
   const int D = g.depth;
-  const bool fuse = fused_merge(e, g);
   // poison, resolver sequence, device error: adjacent words (round_ctl.h)
   HIP_TRY(hipMemsetAsync(e->cursor.p + CTL_POISON, 0, (CTL_ERROR - CTL_POISON + 1) * 8, e->rs[0]));
-  if (fuse) HIP_TRY(hipMemsetAsync(e->tickets.p, 0, (size_t)kMaxDepth * kMaxB * 4, e->rs[0]));
   if (D > 1) {  // the other round streams must not start before that reset
     HIP_TRY(hipEventRecord(e->ev_res[0], e->rs[0]));
     for (int k = 1; k < D; ++k) HIP_TRY(hipStreamWaitEvent(e->rs[k], e->ev_res[0], 0));
@@ -5217,14 +4593,12 @@ int run_batch(kg_engine* e, const RoundGeom& g, int64_t cur, int64_t end, int64_
     const int slot = (int)(r % D);
     hipStream_t st = e->rs[slot];
     size_t t = prof_begin(e, st);
-    launch_eval(e, g, first, nb, slot, st, fuse);
+    launch_eval(e, g, first, nb, slot, st);
     HIP_TRY(hipGetLastError());
     prof_end(e, KG_PROF_EVAL, t, st);
-    if (!fuse) {
-      t = prof_begin(e, st);
-      if (int rc = launch_merge(e, g, nb, slot, st)) return rc;
-      prof_end(e, KG_PROF_MERGE, t, st);
-    }
+    t = prof_begin(e, st);
+    if (int rc = launch_merge(e, g, nb, slot, st)) return rc;
+    prof_end(e, KG_PROF_MERGE, t, st);
     const int n_prev = (int)std::min<int64_t>(r, D - 1);
     t = prof_begin(e, st);
     launch_resolve(e, g, first, nb, slot, n_prev, r + 1, D > 1 && r > 0, st);
@@ -5298,17 +4672,16 @@ int prepare_rounds(kg_engine* e, RoundGeom& g) {
   g = geometry(e);
   if (g.N > kMaxNodes) return fail(KG_E_UNSUPPORTED, "n_nodes %lld > %lld", (long long)g.N, (long long)kMaxNodes);
   // the merge's capacity in lists per pod: one merge_round block holds kMergeThreads·kMergeChunks tile lists (the NUMA
-  // and DeviceShare passes, KG_MERGE=block), one merge_wave wavefront 8·kWave tile or tile-group lists — every shard
+  // and DeviceShare passes), one merge_wave wavefront 8·kWave tile or tile-group lists — every shard
   // of at most kMaxNodes nodes, so the node-count bound above is the round engine's only one
-  const bool block_merge = e->numa_on || e->ds_on || merge_block();
+  const bool block_merge = e->numa_on || e->ds_on;
   if (eval_lists(e, g) > (block_merge ? kMergeThreads * kMergeChunks : 8 * kWave))
     return fail(KG_E_UNSUPPORTED, "%lld nodes per rank exceed one merge %s (%d lists per pod)", (long long)g.shard,
                 block_merge ? "block" : "wavefront", block_merge ? kMergeThreads * kMergeChunks : 8 * kWave);
   // the LDS of a full round of the resolver these rounds launch (the two-wave NUMA resolver only runs where it fits)
-  const size_t lds = e->ds_on               ? ds_lds(g.B, e->nq, e->n_ranks > 1, g.bitmap_words).bytes()
-                     : e->numa_on           ? numa_lds(g.B, g.bitmap_words).bytes()
-                     : !resolver_one_wave() ? mw_lds(g.B).bytes()
-                                            : resolve_lds(g.B, g.bitmap_words).bytes();
+  const size_t lds = e->ds_on     ? ds_lds(g.B, e->nq, e->n_ranks > 1, g.bitmap_words).bytes()
+                     : e->numa_on ? numa_lds(g.B, g.bitmap_words).bytes()
+                                  : resolve_lds(g.B, g.bitmap_words).bytes();
   if (lds > kMaxLds)
     return fail(KG_E_UNSUPPORTED, "%sresolver LDS %zu B > %zu B: fewer nodes or a smaller batch_pods",
                 e->ds_on ? "DeviceShare " : e->numa_on ? "NodeNUMAResource " : "", lds, kMaxLds);
@@ -5926,8 +5299,6 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
   if (hipMemsetAsync(e->cursor.p, 0, CTL_WORDS * 8, e->stream) != hipSuccess) return bail(fail(KG_E_DEVICE, "hipMemset"));
   if (int rc = e->modlists.ensure(kMaxDepth * kModListStride)) return bail(rc);
   if (hipMemsetAsync(e->modlists.p, 0, kMaxDepth * kModListStride * 4, e->stream) != hipSuccess) return bail(fail(KG_E_DEVICE, "hipMemset"));
-  if (int rc = e->tickets.ensure(kMaxDepth * kMaxB)) return bail(rc);
-  if (hipMemsetAsync(e->tickets.p, 0, kMaxDepth * kMaxB * 4, e->stream) != hipSuccess) return bail(fail(KG_E_DEVICE, "hipMemset"));
   e->nodes.assign(cap, kg_node{});
   e->metrics.assign(cap, kg_node_metric{});
   e->folded_usage.assign(2 * cap, 0);
@@ -6123,11 +5494,7 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
 #define KG_ATTR(X)                                                                                           \
   fe = hipFuncSetAttribute((const void*)resolve_round<X, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
   if (fe == hipSuccess)                                                                                      \
-    fe = hipFuncSetAttribute((const void*)resolve_round<X, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-  if (fe == hipSuccess)                                                                                      \
-    fe = hipFuncSetAttribute((const void*)resolve_mw<X, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-  if (fe == hipSuccess)                                                                                      \
-    fe = hipFuncSetAttribute((const void*)resolve_mw<X, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)
+    fe = hipFuncSetAttribute((const void*)resolve_round<X, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)
     KG_PF_SWITCH(profile_bits(e->P), KG_ATTR)
 #undef KG_ATTR
     if (fe != hipSuccess) return bail(fail(KG_E_DEVICE, "hipFuncSetAttribute(resolve_round LDS)"));
@@ -6228,7 +5595,6 @@ void kg_engine_destroy(kg_engine* e) {
   e->out_keys.release();
   e->cursor.release();
   e->modlists.release();
-  e->tickets.release();
   for (int k = 0; k < kMaxDepth; ++k) {
     if (e->ev_res[k]) (void)hipEventDestroy(e->ev_res[k]);
     if (e->rs[k]) (void)hipStreamDestroy(e->rs[k]);
@@ -6793,7 +6159,7 @@ static int schedule_staged_impl(kg_engine* e, int64_t first, int64_t count, kg_s
     std::memset(stats, 0, sizeof(*stats));
     stats->device_batches = host_stats[CTL_ROUNDS];
     stats->reserved[0] = (double)host_stats[CTL_SLOW];  // diagnostics: slow-path pods, speculation steps (resolve_round)
-    stats->reserved[1] = (double)host_stats[CTL_HELPER_WAITS];
+    stats->reserved[1] = 0;  // no counter behind it (CTL_RESERVED_7)
     stats->reserved[2] = (double)host_stats[CTL_ACTIVE_TICKS] * 1e-8;  // resolvers' active time (s_memrealtime, 100 MHz): after the
                                                          // chain wait to the publish, summed over the call's rounds
     stats->node_evaluations = count * g.N;

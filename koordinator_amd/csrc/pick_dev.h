@@ -13,7 +13,7 @@
 // those criteria from the most significant bit down, the position last: the key is unique per candidate, the minimum
 // does not depend on how the candidates are split over lanes, waves and blocks.
 //
-// Three plain launches on the engine stream, in stream order (no spin on another kernel, no tickets, no cooperative
+// Three plain launches on the engine stream, in stream order (no spin on another kernel, no cooperative
 // launch, no atomics on the result), over scratch of their own (the engine's pick_buf):
 //   pick_keys    one wavefront per candidate, the lanes striding its victim segment 64 entries a step (coalesced reads
 //                of kept / priority / start).  Per step one ballot of "kept": its find-first in the first non-empty

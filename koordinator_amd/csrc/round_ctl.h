@@ -21,7 +21,7 @@ enum CtlWord : int {
   CTL_SEQ = 4,           // sequence number of the last resolver that published
   CTL_ERROR = 5,         // device error: a resolver's chain wait timed out
   CTL_SLOW = 6,          // diagnostics: pods re-scored on the chain
-  CTL_HELPER_WAITS = 7,  // diagnostics: pods for which the chain waited on a helper wave (resolve_mw)
+  CTL_RESERVED_7 = 7,    // unused: no kernel writes it, and the words after it keep their indices
   CTL_ACTIVE_TICKS = 8,  // resolvers' active time, s_memrealtime ticks
   CTL_WORDS = 16
 };

@@ -192,56 +192,6 @@ __host__ __device__ constexpr XrLds xr_lds(int xf, int nq, bool aux, int bitmap_
   return L;
 }
 
-// ---- resolve_mw<PF, QUOTA> (KG_RESOLVER=mw) ------------------------------------------------------------------------
-constexpr int kHelpers = 5;         // helper waves
-constexpr int kLag = kHelpers + 1;  // helper(j) scores pod j on the table after pods ≤ j − kLag
-constexpr int kTop = kLag;          // candidates per pod handed to the chain (> |S| = kLag − 1)
-struct MwLds : LdsLayout {
-  // uint64 sections, in 8-byte words from smem: the unit of the row offsets the kernel passes between its waves
-  uint32_t cand, podw, par, prow, toprow, state, top;
-  // uint32 sections, as indices from the byte offset u32 (the kernel keeps one base pointer for them)
-  uint32_t u32, topx, win, wslot, nsl, ready, slot_node, slot_row, hash, prevn, sctl;
-};
-__host__ __device__ constexpr MwLds mw_lds(int nb) {
-  MwLds L{};
-  uint32_t w = 0;  // both groups are counted in their own unit and handed to the carver as one section each
-  const auto words = [&w](uint32_t count) {
-    const uint32_t at = w;
-    w += count;
-    return at;
-  };
-  L.cand = words(nb * kCandStride);  // (LDS-DMA: a 16-B multiple from the 16-B aligned start)
-  L.podw = words(nb * kPodWords);    // (LDS-DMA: likewise)
-  L.par = words(kParWords);
-  // slots of earlier rounds ≤ (depth − 1) · batch ≤ kMaxMod − nb (RoundGeom keeps depth · batch ≤ kMaxMod)
-  L.prow = words((kMaxMod - nb) * kEvalRowWords);  // earlier rounds' rows (slots < nP)
-  L.toprow = words(nb * kTop * kEvalRowWords);     // rows of listed candidates past the staged ones
-  L.state = words(nb * kEvalRowWords);             // the winner's row after pod j's assume
-  L.top = words(nb * kTop);
-  LdsCarver c;
-  c.take<uint64_t, 16>(w);
-  L.u32 = c.bytes();
-  uint32_t i = 0;
-  const auto idx = [&i](uint32_t count) {
-    const uint32_t at = i;
-    i += count;
-    return at;
-  };
-  L.topx = idx(nb * kTop);
-  L.win = idx(nb);
-  L.wslot = idx(nb);
-  L.nsl = idx(nb);    // slots in use after pod j
-  L.ready = idx(nb);  // helper(j) done
-  L.slot_node = idx(kMaxMod);
-  L.slot_row = idx(kMaxMod);  // LDS word offset of the slot's round-start row
-  L.hash = idx(kModHash);
-  L.prevn = idx(kMaxMod);
-  L.sctl = idx(8);  // [0] pods published, [1] chain ended, [2] abort, [3] nP, [4] error, [5] states kept
-  c.take<uint32_t>(i);
-  L.end = c.bytes();
-  return L;
-}
-
 // ---- eval_round ----------------------------------------------------------------------------------------------------
 // A block of ew waves (tiles of tile_nodes nodes) × ppw pods.  On tile groups (`combine`) each wave stages its pods'
 // values of its tile, ew · ppw · tile_nodes uint32 as [pod][tile][lane][j] — a wave's stores and the selecting wave's
@@ -249,8 +199,7 @@ __host__ __device__ constexpr MwLds mw_lds(int nb) {
 // selected.  4 KiB per pod at the 1,024-node group: 32 KiB at ppw = 8, two blocks per CU resident as the kernel's four
 // waves per SIMD allow.  A block whose staging would pass kEvalStageCap (ppw > 15 there) does not stage: two blocks
 // would no longer share a CU's 160 KiB, and the launch would need the large-LDS opt-in; such a pod group, and a shard without tile groups,
-// parks tile lists instead: [ew][max(ppw·kR, kC)] uint64, ppw lists of kR keys per wave (the stride the kernel indexes
-// with).  The fused merge tail reuses the start of the allocation for a pod's kC keys per wave (`lists` either way).
+// parks tile lists instead: [ew][ppw·kR] uint64, ppw lists of kR keys per wave (the stride the kernel indexes with).
 constexpr uint32_t kEvalStageCap = 64 * 1024;
 struct EvalLds : LdsLayout {
   uint32_t lists, vals, sel;
@@ -259,14 +208,13 @@ struct EvalLds : LdsLayout {
 __host__ __device__ constexpr EvalLds eval_lds(int ew, int tile_nodes, int rg, int ppw, bool combine) {
   LdsCarver c;
   EvalLds L{};
-  const uint32_t tail = (uint32_t)ew * kC * 2;  // the fused tail's keys, in uint32 words
   const uint32_t vals = (uint32_t)ew * (uint32_t)ppw * (uint32_t)tile_nodes;
   L.staged = combine && vals * 4u + (uint32_t)(ew * rg) * 8u <= kEvalStageCap;
   if (L.staged) {
-    L.vals = L.lists = c.take<uint32_t, 16>(vals > tail ? vals : tail);  // [ppw][ew][kWave][tile_nodes / kWave]
-    L.sel = c.take<uint64_t, 16>(ew * rg);                               // [ew][rg] selected keys, before their ranking
+    L.vals = L.lists = c.take<uint32_t, 16>(vals);  // [ppw][ew][kWave][tile_nodes / kWave]
+    L.sel = c.take<uint64_t, 16>(ew * rg);          // [ew][rg] selected keys, before their ranking
   } else {
-    L.lists = c.take<uint64_t, 16>(ew * (ppw * kR > kC ? ppw * kR : kC));
+    L.lists = c.take<uint64_t, 16>(ew * ppw * kR);  // [ew][ppw][kR]
   }
   L.end = c.bytes();
   return L;
@@ -280,7 +228,6 @@ __host__ __device__ constexpr EvalLds eval_lds(int ew, int tile_nodes, int rg, i
 // resolve_round_numa where it does not fit.
 constexpr int kMaxBitmapWords = (int)(kMaxNodes / 32);
 static_assert(resolve_lds(kMaxB, kMaxBitmapWords).bytes() <= kMaxLds, "resolve_round at kMaxB pods, kMaxNodes nodes");
-static_assert(mw_lds(kMaxB).bytes() <= kMaxLds, "resolve_mw at kMaxB pods");
 // eval_round at its shape (8 waves of 128-node tiles, 8 keys per group list): two blocks of 8 pods per wave share a CU
 // with their values staged; past kEvalStageCap a block parks tile lists, which fit the default dynamic-LDS limit at
 // any pod count

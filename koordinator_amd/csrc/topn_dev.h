@@ -1,7 +1,7 @@
 // kg_debug_topn (ABI 18): the top-N per-plugin score table of one pod, ranked on the device — what koord-scheduler's
 // --debug-scores prints (frameworkext/debug.go:61-108) without copying an n-row vector per plugin to the host.
 //
-// Four plain launches on the engine stream, in stream order (no spin on another kernel, no tickets, no cooperative
+// Four plain launches on the engine stream, in stream order (no spin on another kernel, no cooperative
 // launch), over scratch of their own (the engine's topn_buf): nothing a schedule call reads later is written.
 //   topn_eval    one thread per node: rsv_eval_node — the per-node body of the exact pass, which also serves single-pod
 //                schedule calls of every profile (wide, NodeNUMAResource only, DeviceShare only, exact) — packed with

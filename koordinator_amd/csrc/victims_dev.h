@@ -8,7 +8,7 @@
 // Every list is stored in MoreImportantPod order (priority descending, earlier start first, ties in the caller's
 // order: the host sorts at set time), so a call never sorts: a subset of a sorted list is sorted.
 //
-// Plain launches on the engine stream, in stream order (no spin on another kernel, no tickets, no cooperative launch,
+// Plain launches on the engine stream, in stream order (no spin on another kernel, no cooperative launch,
 // no atomics):
 //   bp_scatter   set time: one wavefront per replaced list copies it from the staging arrays to its place in the slab
 //                and writes the node's directory entry.

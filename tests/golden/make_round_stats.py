@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Writes tests/golden/round_stats.json: the kg_stats of the schedule calls of tests/round_stats_cases.py.
 
-The fixture pins the control words behind kg_stats (rounds run, pods re-scored on the chain, helper waits) across a
+The fixture pins the control words behind kg_stats (rounds run, pods re-scored on the chain, the reserved word) across a
 change of the resolvers' bookkeeping, so it is recorded against the library built from the commit BEFORE that change,
 on a machine with the GPU:
 

@@ -2,7 +2,7 @@
 case the kg_stats of one kg_pods_schedule call.
 
 The parity tests compare placements, which cannot tell one diagnostic word of the round engine's control blocks from
-another (csrc/round_ctl.h: pods re-scored on the chain, helper waits, rounds run, pods consumed).  kg_stats carries
+another (csrc/round_ctl.h: pods re-scored on the chain, the reserved word, rounds run, pods consumed).  kg_stats carries
 those words to the host, so the cases pin them.  Every case is 300 nodes and 600 pods at batch 16, pipeline depth 1:
 no wide pass overlaps a resolver, so the rounds, their early stops and the counts are deterministic.
 

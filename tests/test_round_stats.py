@@ -1,7 +1,7 @@
 """The control words the parity tests do not see: kg_stats of the schedule calls of tests/round_stats_cases.py equals
 what tests/golden/round_stats.json recorded from the library of the commit before the control blocks got names and the
 resolvers one shared bookkeeping (tests/golden/make_round_stats.py).  A swapped diagnostic word (pods re-scored on
-the chain / helper waits, rounds run / pods consumed) changes these numbers and no placement."""
+the chain / the reserved word, rounds run / pods consumed) changes these numbers and no placement."""
 import functools
 import json
 import os
