@@ -852,6 +852,37 @@ int kg_debug_round_records(kg_engine* e, int64_t first, int64_t nb, int64_t* out
 int kg_debug_merge(kg_engine* e, int variant, const uint64_t* lists, int64_t n_pods, int64_t n_lists, int64_t list_len,
                    uint64_t* out_records);
 
+/* Debug (added within ABI 18; a test hook, not a product path): the round engine's resolver on a staged situation, in
+ * one call on the engine stream, so the outcome does not depend on what overlapping rounds happened to place.
+ *   (a) eval_round + local merge over the staged pods [first, first + nb), nb <= batch_pods, on the table as it
+ *       stands: the snapshot;
+ *   (b) n_prev <= pipeline depth - 1 "earlier rounds still in flight": list d (d = 0 the round just before this one)
+ *       holds prev_counts[d] <= batch_pods placements, the lists concatenated in prev_pods (staged pod index) /
+ *       prev_nodes.  Each placement's terms are added to its node's columns as a round's write-back adds them (aux
+ *       columns included, no quota charge), and the nodes are written to the modified-row lists the resolver reads,
+ *       duplicates as given;
+ *   (c) the control block: cursor = first, everything else 0.  flags KG_DBG_RESOLVE_POISON leaves poison set,
+ *       KG_DBG_RESOLVE_CURSOR puts the cursor at `cursor` instead (a stale round);
+ *       out_keys[first, first + nb) = KG_DBG_RESOLVE_SENTINEL;
+ *   (d) the resolver as a batch launches its round n_prev (round slot n_prev, no chain wait), the quota instantiation
+ *       when a quota table is set.
+ * The table afterwards holds (b) plus the round's write-back.
+ *   out_info    int64[KG_DBG_RESOLVE_WORDS]: cursor, rounds, consumed, poison, sequence, error, slow-path pods, length
+ *               of the list this round published, then the constants a model needs: keys per record (kC), staged rows
+ *               per record, bank-1 probe length, hash slots, score_bits, pipeline depth, round slot, 1 with quotas
+ *   out_records uint64[nb][kC + 1]: the records the resolver consumed (keys, then ub)
+ *   out_keys    uint64[nb]: the engine's result keys of pods [first, first + nb)
+ *   out_list    int32[batch_pods]: the nodes this round published
+ * KG_E_UNSUPPORTED as kg_debug_round_records; KG_E_INVALID: a range outside the staged queue or longer than a round, too
+ * many earlier rounds or placements, a pod or node index out of range. */
+#define KG_DBG_RESOLVE_WORDS 16
+#define KG_DBG_RESOLVE_POISON 1
+#define KG_DBG_RESOLVE_CURSOR 2
+#define KG_DBG_RESOLVE_SENTINEL 0xA5A5A5A5A5A5A5A5ull
+int kg_debug_resolve(kg_engine* e, int64_t first, int64_t nb, int64_t n_prev, const int64_t* prev_counts,
+                     const int32_t* prev_pods, const int32_t* prev_nodes, int64_t flags, int64_t cursor,
+                     int64_t* out_info, uint64_t* out_records, uint64_t* out_keys, int32_t* out_list);
+
 /* Diagnostic builds (-DKG_STAMPS) only: copies the in-kernel (s_memtime, s_memrealtime) stamps, uint64[4][32][2],
  * then the last resolver launch's per-pod (s_memtime, path bits, sub-phase stamps), uint64[64][6], then the NUMA
  * hint-merge counters (merges, all-permutation fallback passes), uint64[2]: 258 + 384 words in all. */

@@ -57,6 +57,11 @@ RSV_EVAL_WORDS = 16  # KG_RSV_EVAL_WORDS: kg_pods_evaluate_reservation per node
 DBG_MERGE_WORDS = 32  # KG_DBG_MERGE_WORDS: one kg_debug_numa_merge case
 DBG_GEOM_WORDS = 8  # KG_DBG_GEOM_WORDS: kg_debug_round_records' geometry words, named by DBG_GEOM_FIELDS
 DBG_GEOM_FIELDS = ("tile_nodes", "group_tiles", "combined", "n_lists", "list_len", "kc", "score_bits")
+DBG_RESOLVE_WORDS = 16  # KG_DBG_RESOLVE_WORDS: kg_debug_resolve's out_info words, named by DBG_RESOLVE_FIELDS
+DBG_RESOLVE_FIELDS = ("cursor", "rounds", "consumed", "poison", "seq", "error", "slow", "n_list", "kc", "staged",
+                      "bank1_probe", "mod_hash", "score_bits", "depth", "slot", "quota")
+DBG_RESOLVE_POISON, DBG_RESOLVE_CURSOR = 1, 2  # KG_DBG_RESOLVE_*: flags
+DBG_RESOLVE_SENTINEL = 0xA5A5A5A5A5A5A5A5  # KG_DBG_RESOLVE_SENTINEL: out_keys before the resolver runs
 REJECT_FIT_OTHER = 128  # NodeResourcesFit: ephemeral-storage / a scalar resource (RES_EPHEMERAL .. RES_MID_MEMORY)
 REJECT_RESERVATION = 256  # Reservation Filter (kg_pods_filter_preemption)
 REJECT_SPREAD = 512  # (ABI 12) PodTopologySpread
@@ -262,7 +267,7 @@ EXPORTED_SYMBOLS = (
     "kg_engine_create_hosted", "kg_pods_filter_preemption", "kg_nodes_read_pod_groups",
     "kg_pods_select_victims", "kg_debug_topn", "kg_pods_diagnose", "kg_pods_pick_candidate", "kg_pods_preempt",
     "kg_node_bound_pods_set", "kg_nodes_read_bound_pods", "kg_pods_select_victims_resident",
-    "kg_pods_preempt_resident", "kg_debug_round_records", "kg_debug_merge",
+    "kg_pods_preempt_resident", "kg_debug_round_records", "kg_debug_merge", "kg_debug_resolve",
     "kg_nominated_pods_set", "kg_nominated_pods_read", "kg_pods_schedule_staged_nominated",
     "kg_pods_filter_nominated", "kg_nominated_counters",
 )
@@ -331,6 +336,7 @@ def load_library(path: str | None = None):
         "kg_debug_eval_paths": (i, [vp, vp]),
         "kg_debug_round_records": (i, [vp, i64, i64, vp, vp, i64, vp]),
         "kg_debug_merge": (i, [vp, i, vp, i64, i64, i64, vp]),
+        "kg_debug_resolve": (i, [vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp, vp]),
         "kg_debug_stamps": (i, [vp, vp]),
         "kg_debug_fast_lrs": (i, [vp, vp, vp, vp, vp, i64]),
         "kg_nodes_numa_upsert": (i, [vp, vp, vp, i64]),

@@ -1108,7 +1108,8 @@ __device__ __forceinline__ void assume_mod(EvalRow& e, const DevPod& p, const Ev
   if (out) e.flags |= F_RARE;
 }
 
-// wave max of packed keys: one 32-bit DPP max when (score, node) fit 13 + 19 bits, else the two-word form
+// wave max of packed keys: one 32-bit DPP max when (score, node) fit 13 + 19 bits, else the two-word form.  The
+// narrow form reads 0 as "no key", so its caller keeps it off tables that hold node 2^19 − 1 (score 0 there packs to 0)
 __device__ __forceinline__ uint64_t wave_max_modkey(uint64_t k, bool narrow) {
   if (narrow) {
     const uint32_t k32 = k ? (uint32_t)((k >> 32) << 19) | (0x7FFFFu - key_node(k)) : 0u;
@@ -1141,6 +1142,14 @@ __device__ __forceinline__ void writeback_pod(const DevTable& T, uint32_t node, 
 #pragma unroll
     for (int r = 0; r < kAux; ++r)
       if (rq[r]) add(&T.aux[(size_t)(kAux + r) * T.cap + i], rq[r]);
+}
+
+// kg_debug_resolve's "earlier rounds": placement k puts staged pod pod_idx[k] on node[k], with the write-back above
+__global__ void debug_assume_pods(DevTable T, const DevPod* __restrict__ pods, const int64_t* __restrict__ paux,
+                                  const int32_t* __restrict__ pod_idx, const int32_t* __restrict__ node, int64_t n) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  writeback_pod(T, (uint32_t)node[k], pods[pod_idx[k]], paux + (size_t)pod_idx[k] * kAux);
 }
 
 // fitsRequest over the kAux resources on a modified row: the round-start Requested (the table; this round's
@@ -1296,7 +1305,9 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
       atomicOr(&bitmap[node >> 5], 1u << (node & 31));
     }
   }
-  const bool narrow = P.score_bits <= 13;  // packed keys fit 32 bits (node < 2^19 = kMaxNodes)
+  // packed keys fit 32 bits (13 + 19), and 0 stays "no key": score 0 on node 2^19 − 1 would pack to 0, so a table
+  // that can hold that node (its bitmap is the full kMaxBitmapWords) takes the two-word maximum
+  const bool narrow = P.score_bits <= 13 && bitmap_words < kMaxBitmapWords;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // LDS-DMA of records and pods (+ the rows above)
   __syncthreads();
   // ElasticQuota table (QUOTA instantiation only), after the chain wait: the previous resolver's charges are visible
@@ -6781,6 +6792,111 @@ int kg_debug_merge(kg_engine* e, int variant, const uint64_t* lists, int64_t n_p
   if (he != hipSuccess) return done(fail(KG_E_DEVICE, "kg_debug_merge: %s", hipGetErrorString(he)));
   for (int64_t p = 0; p < n_pods; ++p)
     std::memcpy(out_records + (size_t)p * (kC + 1), rec.data() + (size_t)p * kCandStride, (kC + 1) * 8);
+  return done(0);
+}
+
+// kg_debug_resolve: the product's resolver on a staged situation (tests/test_resolver_branches.py).  One call, one
+// stream: eval + merge on the table as it stands (the snapshot), the caller's "earlier rounds" written onto the table
+// and into the modified-row lists, the control words, then launch_resolve as run_batch issues it.  Not a product path.
+int kg_debug_resolve(kg_engine* e, int64_t first, int64_t nb, int64_t n_prev, const int64_t* prev_counts,
+                     const int32_t* prev_pods, const int32_t* prev_nodes, int64_t flags, int64_t cursor,
+                     int64_t* out_info, uint64_t* out_records, uint64_t* out_keys, int32_t* out_list) {
+  if (!e || !out_info || !out_records || !out_keys || !out_list) return fail(KG_E_INVALID, "null argument");
+  if (e->numa_on || e->ds_on || e->exact_on || e->n_ranks > 1)
+    return fail(KG_E_UNSUPPORTED, "the Fit + LoadAware round engine on one rank only");
+  RoundGeom g;
+  if (int rc = prepare_rounds(e, g)) return rc;
+  if (first < 0 || nb < 1 || nb > g.B || first + nb > e->n_staged)
+    return fail(KG_E_INVALID, "pods [%lld, %lld): a round of at most %d staged pods (%lld staged)", (long long)first,
+                (long long)(first + nb), g.B, (long long)e->n_staged);
+  if (n_prev < 0 || n_prev > g.depth - 1)
+    return fail(KG_E_INVALID, "%lld earlier rounds: the engine's depth %d keeps at most %d in flight", (long long)n_prev,
+                g.depth, g.depth - 1);
+  if (flags & ~(int64_t)(KG_DBG_RESOLVE_POISON | KG_DBG_RESOLVE_CURSOR)) return fail(KG_E_INVALID, "unknown flag");
+  int64_t total = 0;
+  for (int64_t d = 0; d < n_prev; ++d) {
+    if (!prev_counts || prev_counts[d] < 0 || prev_counts[d] > g.B)
+      return fail(KG_E_INVALID, "earlier round %lld: a list holds 0..%d placements", (long long)d, g.B);
+    total += prev_counts[d];
+  }
+  if (total > 0 && (!prev_pods || !prev_nodes)) return fail(KG_E_INVALID, "null argument");
+  for (int64_t k = 0; k < total; ++k)
+    if (prev_pods[k] < 0 || prev_pods[k] >= e->n_staged || prev_nodes[k] < 0 || prev_nodes[k] >= e->n_nodes)
+      return fail(KG_E_INVALID, "placement %lld: staged pod %d on node %d", (long long)k, prev_pods[k], prev_nodes[k]);
+  // the round r = n_prev of a batch: slot r % depth, its predecessors in the slots before it
+  const int slot = (int)n_prev;
+  hipStream_t st = e->stream;
+  DevBuf<int32_t> dpairs;
+  auto done = [&](int rc) {
+    dpairs.release();
+    return rc;
+  };
+  // (a) the snapshot: this round's wide pass and merge
+  HIP_TRY(hipMemsetAsync(e->cursor.p + CTL_POISON, 0, sizeof(int64_t), st));
+  launch_eval(e, g, first, (int)nb, slot, st);
+  HIP_TRY(hipGetLastError());
+  launch_merge_local(e, g, (int)nb, slot, st);
+  HIP_TRY(hipGetLastError());
+  // (b) what the earlier rounds placed after it: onto the table, and into the lists of their slots as given
+  std::vector<int32_t> ml((size_t)kMaxDepth * kModListStride, 0);
+  {
+    int64_t k = 0;
+    for (int64_t d = 0; d < n_prev; ++d) {  // d = 0: the round just before this one
+      int32_t* l = ml.data() + (size_t)(slot - 1 - d) * kModListStride;
+      l[0] = (int32_t)prev_counts[d];
+      for (int64_t t = 0; t < prev_counts[d]; ++t, ++k) l[1 + t] = prev_nodes[k];
+    }
+  }
+  if (hipMemcpyAsync(e->modlists.p, ml.data(), ml.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess)
+    return done(fail(KG_E_DEVICE, "kg_debug_resolve: hipMemcpy"));
+  if (total > 0) {
+    if (int rc = dpairs.ensure((size_t)2 * total)) return done(rc);
+    hipError_t he = hipMemcpyAsync(dpairs.p, prev_pods, (size_t)total * 4, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(dpairs.p + total, prev_nodes, (size_t)total * 4, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) {
+      debug_assume_pods<<<(unsigned)((total + 63) / 64), 64, 0, st>>>(e->T, e->pods.p, e->paux.p, dpairs.p,
+                                                                    dpairs.p + total, total);
+      he = hipGetLastError();
+    }
+    if (he != hipSuccess) {
+      (void)hipStreamSynchronize(st);
+      return done(fail(KG_E_DEVICE, "kg_debug_resolve: %s", hipGetErrorString(he)));
+    }
+  }
+  // (c) the control words (the whole block, as a schedule call writes it) and the sentinel over this round's keys
+  int64_t ctl[CTL_WORDS] = {};
+  ctl[CTL_CURSOR] = (flags & KG_DBG_RESOLVE_CURSOR) ? cursor : first;
+  ctl[CTL_POISON] = (flags & KG_DBG_RESOLVE_POISON) ? 1 : 0;
+  std::vector<uint64_t> keys((size_t)nb, (uint64_t)KG_DBG_RESOLVE_SENTINEL);
+  hipError_t he = hipMemcpyAsync(e->cursor.p, ctl, sizeof(ctl), hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) he = hipMemcpyAsync(e->out_keys.p + first, keys.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st);
+  // (d) the resolver, exactly as run_batch launches a batch's round: no wait, the engine's depth and quota table
+  if (he == hipSuccess) {
+    launch_resolve(e, g, first, (int)nb, slot, (int)n_prev, n_prev + 1, 0, st);
+    he = hipGetLastError();
+  }
+  // (e) read back
+  std::vector<uint64_t> rec((size_t)nb * kCandStride);
+  std::vector<int32_t> mine(kModListStride, 0);
+  if (he == hipSuccess) he = hipMemcpyAsync(rec.data(), cand_slot(e, g, slot), rec.size() * 8, hipMemcpyDeviceToHost, st);
+  if (he == hipSuccess) he = hipMemcpyAsync(out_keys, e->out_keys.p + first, (size_t)nb * 8, hipMemcpyDeviceToHost, st);
+  if (he == hipSuccess) he = hipMemcpyAsync(ctl, e->cursor.p, sizeof(ctl), hipMemcpyDeviceToHost, st);
+  if (he == hipSuccess)
+    he = hipMemcpyAsync(mine.data(), e->modlists.p + (size_t)slot * kModListStride, mine.size() * 4,
+                        hipMemcpyDeviceToHost, st);
+  const hipError_t hs = hipStreamSynchronize(st);  // before the buffers go, whatever was queued
+  if (he == hipSuccess) he = hs;
+  if (he != hipSuccess) return done(fail(KG_E_DEVICE, "kg_debug_resolve: %s", hipGetErrorString(he)));
+  for (int64_t p = 0; p < nb; ++p)
+    std::memcpy(out_records + (size_t)p * (kC + 1), rec.data() + (size_t)p * kCandStride, (kC + 1) * 8);
+  // (this round's slot was cleared with the others above: a stale round leaves it empty)
+  const int64_t n_list = std::min<int64_t>(std::max<int32_t>(mine[0], 0), kMaxB);
+  std::memcpy(out_list, mine.data() + 1, (size_t)n_list * 4);
+  const int64_t info[KG_DBG_RESOLVE_WORDS] = {ctl[CTL_CURSOR], ctl[CTL_ROUNDS], ctl[CTL_CONSUMED],
+                                              (int64_t)(int32_t)ctl[CTL_POISON], ctl[CTL_SEQ], ctl[CTL_ERROR],
+                                              ctl[CTL_SLOW], n_list, kC, kStaged, kBank1Probe, kModHash,
+                                              e->P.score_bits, g.depth, slot, e->nq > 0 ? 1 : 0};
+  std::memcpy(out_info, info, sizeof(info));
   return done(0);
 }
 

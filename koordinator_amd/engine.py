@@ -448,6 +448,30 @@ class Engine:
         check(self.lib, self.lib.kg_debug_merge(self.h, int(variant), ptr(lists), n_pods, n_lists, list_len, ptr(out)))
         return out
 
+    def debug_resolve(self, first: int, nb: int, prev=(), poison: bool = False, cursor=None):
+        """The product's resolver on a staged situation (kg_debug_resolve; a test hook): eval + merge of the staged pods
+        [first, first + nb) on the table as it stands, then the earlier rounds `prev` — a sequence of lists of
+        (staged pod index, node) pairs, prev[0] the round just before this one — applied to the table and to the
+        modified-row lists, then the resolver.  poison / cursor: a stale round.  Returns a dict: the control words and
+        constants over abi.DBG_RESOLVE_FIELDS, 'records' uint64[nb, kc + 1], 'out_keys' uint64[nb], 'list' int32[n]."""
+        counts = np.array([len(l) for l in prev], dtype=np.int64)
+        pairs = np.array([pr for l in prev for pr in l], dtype=np.int32).reshape(-1, 2)
+        pods = np.ascontiguousarray(pairs[:, 0])
+        nodes = np.ascontiguousarray(pairs[:, 1])
+        flags = (abi.DBG_RESOLVE_POISON if poison else 0) | (abi.DBG_RESOLVE_CURSOR if cursor is not None else 0)
+        info = np.zeros(abi.DBG_RESOLVE_WORDS, dtype=np.int64)
+        records = np.zeros((int(nb), 65), dtype=np.uint64)  # kC + 1 words per pod; checked against info below
+        keys = np.zeros(int(nb), dtype=np.uint64)
+        lst = np.zeros(64, dtype=np.int32)
+        check(self.lib, self.lib.kg_debug_resolve(self.h, int(first), int(nb), len(counts), ptr(counts), ptr(pods),
+                                                  ptr(nodes), flags, int(cursor or 0), ptr(info), ptr(records),
+                                                  ptr(keys), ptr(lst)))
+        out = dict(zip(abi.DBG_RESOLVE_FIELDS, (int(x) for x in info)))
+        if out["kc"] + 1 != records.shape[1]:
+            raise RuntimeError(f"kg_debug_resolve: records of {out['kc']} keys, the binding sized them for 64")
+        out.update(records=records, out_keys=keys, list=lst[:out["n_list"]].copy())
+        return out
+
     def filter_preemption(self, pod: np.ndarray, node: int, victims: np.ndarray, slots=None, minors=None) -> int:
         """The preemption dry run's Filter of `pod` on node `node` with `victims` removed (kg_pods_filter_preemption):
         KG_REJECT_* bits, 0 = fits.  slots[k]: the node's reservation slot victim k was allocated from (-1 = none);

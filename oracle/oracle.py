@@ -378,6 +378,15 @@ def quota_admit(quota, pod) -> bool:
                                      p(np.ascontiguousarray(np.asarray(pod, dtype=abi.POD_DTYPE).reshape(1)))))
 
 
+def quota_charge(quotas, k: int, pod):
+    """ElasticQuota Reserve of one placed pod against quotas[k] (or_quota_charge; mutates the row)."""
+    quotas = np.asarray(quotas)
+    assert quotas.dtype == abi.QUOTA_DTYPE and quotas.flags["C_CONTIGUOUS"]
+    fn = lib().or_quota_charge
+    fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], None
+    fn(p(quotas[k:k + 1]), p(np.ascontiguousarray(np.asarray(pod, dtype=abi.POD_DTYPE).reshape(1))))
+
+
 def rsv_case(pod, allowed_pods, alloc, num_pods, pod_requested, r_allocated, has_state, rsv):
     """One node's Reservation Filter / nomination / Score with an explicit nodeReservationState, every slot in
     `matched` (how reservation/*_test.go build their states).  Returns (filter_pass, nominated_slot, score)."""
