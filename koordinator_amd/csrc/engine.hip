@@ -32,6 +32,7 @@
 #include "numa_dev.h"
 #include "ds_dev.h"
 #include "round_ctl.h"
+#include "resolve_steps.h"
 #include "round_lds.h"
 #include "rsv_dev.h"
 
@@ -1013,7 +1014,7 @@ __global__ __launch_bounds__(kWave * 4) void merge_wave(DevTable T, EvalParams P
 // The "modified set" of pod j = every node assumed by an earlier pod of this round or by the n_prev rounds before
 // it that were still resolving when this round was evaluated (pipelining depth D: this round's eval read the table
 // right after resolve(r - D), so rows of rounds r-D+1 .. r-1 may have been read mid-update).  Modified rows live
-// in registers: slot s = bank·64 + lane holds node m[bank] as a hoisted EvalRow kept current by assume_on (two
+// in registers: slot s = bank·64 + lane holds node m[bank] as a hoisted EvalRow kept current by assume_mod (two
 // banks: ≤ 128 rows).  Per pod j, for a monotone profile (Fit, LoadAware: an assume only lowers a node's key; a
 // row read as a mix of pre- and post-assume columns reads ≥ its current key):
 //   e     = the best listed candidate not modified (its key is exact);
@@ -1122,6 +1123,7 @@ __device__ __forceinline__ uint64_t wave_max_modkey(uint64_t k, bool narrow) {
 // Round write-back: lane j < consumed adds placed pod j's NodeInfo.AddPod + podAssignCache.assign terms onto its
 // winner's columns (int64 atomics: several pods of the round may share a winner; no other writer — earlier rounds'
 // resolvers are done, later ones wait for this one; concurrent wide passes read mixed columns).
+// The row terms are row_assume's (resolve_steps.h), which the one owner of a row adds without atomics.
 __device__ __forceinline__ void writeback_pod(const DevTable& T, uint32_t node, const DevPod& p,
                                               const int64_t* __restrict__ rq) {
   const int64_t i = node;
@@ -1530,6 +1532,7 @@ __global__ __launch_bounds__(kWave* kEvalWaves) void eval_round_numa(DevTable T,
   }
 }
 
+static_assert(kC == kWave, "first_unmodified: one listed candidate per lane, so its 'none' position kWave is kC");
 // Single-wave FIFO resolver of a NUMA round (unpipelined).  Lane l < nM owns modified node l: its Row in
 // registers, its NUMA state in LDS slot l.  Per pod: e = best unmodified candidate, mbest = exact re-score of
 // every modified row; best < ub ends the round early (as resolve_round).  The winner's owner lane runs
@@ -1583,10 +1586,7 @@ __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTabl
     nM = compact_prev_nodes(s_prevn, n, lane, true);
     if (lane < nM) {
       midx = s_prevn[lane];
-      mrow = load_row(T, midx);
-      s_ns[lane] = NT.s[midx];
-      s_nm[lane] = NT.m[midx];
-      mv = make_view(&s_ns[lane], &s_nm[lane], NP);
+      numa_slot_load(T, NT.s, NT.m, midx, NP, mrow, &s_ns[lane], &s_nm[lane], mv);
       atomicOr(&bitmap[midx >> 5], 1u << (midx & 31));
     }
     __syncthreads();
@@ -1603,22 +1603,16 @@ __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTabl
       ++consumed;
       continue;
     }
-    const uint32_t node = key_node(key);
-    const bool unmod = (key != 0) && !((bitmap[node >> 5] >> (node & 31)) & 1u);
-    const uint64_t um = __ballot(unmod);
-    const int pos = um ? (int)__builtin_ctzll(um) : kC;
-    uint64_t best = um ? readlane_u64(key, pos) : 0;
+    const FirstUnmod e = first_unmodified(key, bitmap);
+    const uint64_t um = e.mask;
+    uint64_t best = e.key;
     // The best unmodified candidate e wins unless a modified row beats it: its row is brought into the spare slot
     // nM before the re-score, so its Filter (the affinity Reserve needs) runs alongside the modified rows' instead
     // of after the search on one lane.  Slot nM only becomes a modified row if e wins.
     if (lane == 0) KG_LANE_SUB(j, 0);
     if (um && lane == nM) {
-      const uint32_t en = key_node(best);
-      midx = en;
-      mrow = load_row(T, en);
-      s_ns[nM] = NT.s[en];
-      s_nm[nM] = NT.m[en];
-      mv = make_view(&s_ns[nM], &s_nm[nM], NP);
+      midx = key_node(best);
+      numa_slot_load(T, NT.s, NT.m, midx, NP, mrow, &s_ns[nM], &s_nm[nM], mv);
     }
     if (lane == 0) KG_LANE_SUB(j, 1);
     NumaHint maff{0, 1, 0, 0};  // the affinity of this lane's row (Reserve reuses it when the row wins)
@@ -1640,12 +1634,9 @@ __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTabl
       continue;
     }
     const uint32_t w = key_node(best);
-    const uint64_t hit = __ballot((lane < nM) & (midx == w));
-    const int owner = hit ? (int)__builtin_ctzll(hit) : nM;
-    if (!hit) {  // w = e, already in slot nM = owner (with its affinity)
-      if (lane == 0) bitmap[w >> 5] |= 1u << (w & 31);
-      ++nM;
-    }
+    const SlotOwner so = slot_owner(lane, midx, nM, w, bitmap);
+    const int owner = so.lane;
+    if (so.fresh) ++nM;  // w = e, already in slot nM = owner (with its affinity)
     __syncthreads();
     KG_POD_SUB(j, 1);
     int placed = 0;
@@ -1679,17 +1670,7 @@ __global__ __launch_bounds__(kWave) void resolve_round_numa(DevTable T, NumaTabl
       if (placed && lane == owner) {
         s_nm[lane] = nm;
         mv = make_view(&s_ns[lane], &s_nm[lane], NP);
-        mrow.req_cpu += p.req_cpu;  // assume: NodeInfo.AddPod + LoadAware assign cache
-        mrow.req_mem += p.req_mem;
-        mrow.nz_cpu += p.nz_cpu;
-        mrow.nz_mem += p.nz_mem;
-        mrow.la_used_cpu += p.est_cpu;
-        mrow.la_used_mem += p.est_mem;
-        if (p.flags & P_PROD) {
-          mrow.la_pused_cpu += p.est_cpu;
-          mrow.la_pused_mem += p.est_mem;
-        }
-        mrow.num_pods += 1;
+        row_assume(mrow, p);
         touched = true;
 #pragma unroll
         for (int q = 0; q < kCpuWords; ++q) out_cpus[(size_t)(first + j) * kCpuWords + q] = cpus.w[q];
@@ -2391,11 +2372,9 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
       }
     }
     const uint32_t Mj = Mrs ? Mrs - 1u : 0u;
-    const uint32_t node = key_node(key);
-    const bool unmod = (key != 0) && !((bitmap[node >> 5] >> (node & 31)) & 1u);
-    const uint64_t um = __ballot(unmod);
-    const int pos = um ? (int)__builtin_ctzll(um) : kC;
-    uint64_t best = um ? readlane_u64(key, pos) : 0;
+    const FirstUnmod e = first_unmodified(key, bitmap);
+    const int pos = e.pos;
+    uint64_t best = e.key;
     // With M_j = the round-start M every plugin term is monotone (an assume only lowers a node's key), so a
     // modified row can only beat the best unmodified candidate when that is not the pod's overall top key.
     if (nM > 0 && (pos != 0 || most)) {
@@ -2412,9 +2391,9 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
       continue;
     }
     const uint32_t w = key_node(best);
-    const uint64_t hit = __ballot((lane < nM) & (midx == w));
-    const int owner = hit ? (int)__builtin_ctzll(hit) : nM;
-    if (!hit) {
+    const SlotOwner so = slot_owner(lane, midx, nM, w, bitmap);
+    const int owner = so.lane;
+    if (so.fresh) {
       const uint64_t sh = __ballot(stg_node == w);  // a pod whose top candidate is w staged its row
       const int src = sh ? (int)__builtin_ctzll(sh) : -1;
       if (lane == owner) {  // copy the row straight into the lane's LDS slots (memcpy: alias-safe, no private copy)
@@ -2427,7 +2406,6 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
           __builtin_memcpy(&s_d0[owner], from, sizeof(DsNode));
         }
       }
-      if (lane == 0) bitmap[w >> 5] |= 1u << (w & 31);
       ++nM;
     }
     __syncthreads();
@@ -2464,17 +2442,7 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
       }
     }
     if (placed && lane == owner) {
-      mrow.req_cpu += p.req_cpu;  // NodeInfo.AddPod + LoadAware assign cache
-      mrow.req_mem += p.req_mem;
-      mrow.nz_cpu += p.nz_cpu;
-      mrow.nz_mem += p.nz_mem;
-      mrow.la_used_cpu += p.est_cpu;
-      mrow.la_used_mem += p.est_mem;
-      if (p.flags & P_PROD) {
-        mrow.la_pused_cpu += p.est_cpu;
-        mrow.la_pused_mem += p.est_mem;
-      }
-      mrow.num_pods += 1;
+      row_assume(mrow, p);
       touched = true;
     }
     placed = __builtin_amdgcn_readlane(placed, owner);
@@ -2978,16 +2946,7 @@ __global__ void unreserve_pods(DevTable T, const DevPod* __restrict__ pods, cons
     const uint32_t w = key_node(key);
     const DevPod p = pods[j];
     Row r = load_row(T, w);  // NodeInfo.RemovePod + podAssignCache.unAssign (pod_assign_cache.go:119-131)
-    const int64_t prod = (p.flags & P_PROD) ? 1 : 0;
-    r.req_cpu -= p.req_cpu;
-    r.req_mem -= p.req_mem;
-    r.nz_cpu -= p.nz_cpu;
-    r.nz_mem -= p.nz_mem;
-    r.la_used_cpu -= p.est_cpu;
-    r.la_used_mem -= p.est_mem;
-    r.la_pused_cpu -= prod * p.est_cpu;
-    r.la_pused_mem -= prod * p.est_mem;
-    r.num_pods -= 1;
+    row_assume(r, p, -1);
     store_mutable(T, w, r);
     if (gpods) group_apply(G, w, gpods[j], -1, hard_w);  // the node's pod-group counters
     if (p.flags & P_AUX)  // ephemeral-storage / scalar Requested

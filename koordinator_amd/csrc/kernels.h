@@ -386,11 +386,6 @@ struct EvalRow {
 static_assert(sizeof(EvalRow) == 144, "EvalRow layout");
 constexpr int kEvalRowWords = 18;  // 144 B in uint64 words
 
-__device__ __forceinline__ float i64_to_f32(int64_t x) {  // x ≥ 0; ~1 ulp, enough for a ±1 quotient estimate
-  const uint64_t u = (uint64_t)x;
-  return fmaf((float)(uint32_t)(u >> 32), 4294967296.0f, (float)(uint32_t)u);
-}
-
 __device__ __forceinline__ bool cpu_dom(int64_t cap, int64_t fr) {
   return cap > 0 && cap < kCpuCapMax && fr >= kCpuFreeMin && fr <= cap;
 }
@@ -442,36 +437,6 @@ __device__ __forceinline__ EvalRow make_eval_row(const Row& r, const EvalParams&
   // the f64 memory terms are exact only inside the domain; outside it the exact path re-reads the table
   e.flags |= rare_bit(e, P);
   return e;
-}
-
-// assume(pod) on a hoisted row: upstream NodeInfo.AddPod + LoadAware Reserve → podAssignCache.assign
-// (load_aware.go:260-263).  Capacities and reciprocals are unchanged; only the free terms move.
-__device__ __forceinline__ void assume_on(EvalRow& e, const DevPod& p, const EvalParams& P) {
-  const bool prod = (p.flags & P_PROD) != 0;
-  e.free_cpu -= p.req_cpu;
-  e.free_mem -= p.req_mem;
-  e.fnz_cpu -= p.nz_cpu;
-  e.fnz_mem -= p.nz_mem_d;
-  e.la_free_cpu -= p.est_cpu;
-  e.la_free_mem -= p.est_mem_d;
-  e.la_pfree_cpu -= prod ? p.est_cpu : 0;
-  e.la_pfree_mem -= prod ? p.est_mem_d : 0.0;
-  e.pods_left -= 1;
-  e.flags = (e.flags & ~F_RARE) | rare_bit(e, P);
-}
-
-// Mutable columns recovered from a hoisted row (inverse of make_eval_row; exact inside the domain).
-__device__ __forceinline__ void store_eval_row(const DevTable& T, int64_t i, const EvalRow& e) {
-  const int64_t am = (int64_t)e.alloc_mem, lam = (int64_t)e.la_alloc_mem;
-  T.req_cpu[i] = e.alloc_cpu - e.free_cpu;
-  T.req_mem[i] = am - e.free_mem;
-  T.nz_cpu[i] = e.alloc_cpu - e.fnz_cpu;
-  T.nz_mem[i] = am - (int64_t)e.fnz_mem;
-  T.la_used_cpu[i] = e.la_alloc_cpu - e.la_free_cpu;
-  T.la_used_mem[i] = lam - (int64_t)e.la_free_mem;
-  T.la_pused_cpu[i] = e.la_alloc_cpu - e.la_pfree_cpu;
-  T.la_pused_mem[i] = lam - (int64_t)e.la_pfree_mem;
-  T.num_pods[i] = e.alloc_pods - e.pods_left - 1;
 }
 
 __device__ __forceinline__ Row row_of(const EvalRow& e) {  // the reference-shaped row behind a hoisted one

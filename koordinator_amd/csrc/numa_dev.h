@@ -80,9 +80,6 @@ __device__ __forceinline__ CpuSet cs_zero() { return CpuSet{{0, 0, 0, 0}}; }
 __device__ __forceinline__ int cs_count(const CpuSet& s) {
   return __popcll(s.w[0]) + __popcll(s.w[1]) + __popcll(s.w[2]) + __popcll(s.w[3]);
 }
-__device__ __forceinline__ bool cs_has(const CpuSet& s, int c) { return (s.w[c >> 6] >> (c & 63)) & 1ull; }
-__device__ __forceinline__ void cs_set(CpuSet& s, int c) { s.w[c >> 6] |= 1ull << (c & 63); }
-__device__ __forceinline__ void cs_clr(CpuSet& s, int c) { s.w[c >> 6] &= ~(1ull << (c & 63)); }
 // cpus [lo, hi)
 __device__ __forceinline__ CpuSet cs_range(int lo, int hi) {
   CpuSet s;
@@ -113,9 +110,7 @@ __device__ __forceinline__ CpuSet cs_or(CpuSet a, const CpuSet& b) {
 
 struct Topo {
   int sockets, nps, cpn, cpc, nodes, cores, cpus;
-  __device__ int core_of(int c) const { return c / cpc; }
   __device__ int node_of(int c) const { return c / (cpc * cpn); }
-  __device__ int socket_of(int c) const { return c / (cpc * cpn * nps); }
   __device__ int per_node() const { return cpc * cpn; }
   __device__ int per_socket() const { return cpc * cpn * nps; }
   __device__ CpuSet all() const { return cs_range(0, cpus); }
@@ -285,15 +280,6 @@ __device__ __forceinline__ void order_groups(const Acc& a, bool by_node, const C
     k[g] = key;
   }
   sort8(k);
-}
-
-// first k cpus of a group list where cores are ordered (free count desc, id) and cpus ascending (cpc ≤ 2:
-// full cores then single-cpu cores, each ascending)
-__device__ __forceinline__ CpuSet first_k_cores_order(const Topo& t, const CpuSet& s, int k) {
-  const CpuSet full = full_core_cpus(t, s);
-  const int nf = cs_count(full);
-  if (k <= nf) return lowest_k(full, k);
-  return cs_or(full, lowest_k(cs_andnot(s, full), k - nf));
 }
 
 // spreadCPUs over an ascending cpu list: the first cpu of every core (ascending), then the rest (ascending);

@@ -36,7 +36,7 @@ constexpr int kParWords = (int)((sizeof(EvalParams) + 7) / 8);
 constexpr int kRowWords = (int)(sizeof(Row) / 8);
 constexpr int kNumaStaticWords = (int)(sizeof(NumaStatic) / 8), kNumaMutWords = (int)(sizeof(NumaMut) / 8);
 constexpr int kNumaPodWords = (int)(sizeof(NumaPod) / 8), kViewWords = (int)(sizeof(NumaView) / 8);
-constexpr int kDsNodeWords = (int)(sizeof(DsNode) / 8), kDsPodWords = (int)(sizeof(DsPod) / 8);
+constexpr int kDsPodWords = (int)(sizeof(DsPod) / 8);
 constexpr int kRsvPodWords = (int)(sizeof(RsvPod) / 8), kDefPodWords = (int)((sizeof(DefPod) + 7) / 8);
 static_assert(sizeof(Row) % 8 == 0 && sizeof(NumaView) % 8 == 0 && sizeof(NumaStatic) % 8 == 0 &&
                   sizeof(NumaMut) % 8 == 0 && sizeof(NumaPod) % 8 == 0 && sizeof(DsNode) % 8 == 0 &&

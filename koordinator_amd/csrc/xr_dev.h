@@ -42,10 +42,6 @@ __device__ __forceinline__ uint64_t xr_wave_maxcount(uint32_t m, uint32_t c) {
   const uint32_t wc = wave_sum_u32(m == wm ? c : 0u);
   return ((uint64_t)wm << 32) | wc;
 }
-__device__ __forceinline__ void xr_acc(uint32_t v, uint32_t& m, uint32_t& c) {
-  c = v > m ? 1u : c + (v == m && v != 0 ? 1u : 0u);
-  m = v > m ? v : m;
-}
 __device__ __forceinline__ void xr_tile_coords(int n_pg, int& tile, int& p0) {
   const int wave = threadIdx.x / kWave;
   const uint32_t nwg = gridDim.x, bid = blockIdx.x, xcd = bid % 8u, q = nwg / 8u, r = nwg % 8u;

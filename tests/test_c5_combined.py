@@ -11,6 +11,8 @@ the DeviceShare free table, the quotas' used / non-preemptible-used and the Node
 import numpy as np
 import pytest
 
+import test_fit_aux as TA
+import test_parity_gpu as TP
 from koordinator_amd import Engine, abi, framework as F, synth
 from oracle import oracle
 
@@ -63,7 +65,8 @@ def test_oracle_quota_off_equals_plain_profile():
         assert np.array_equal(a[k], b[k]), k
 
 
-def engine_run(cfg, cluster, dev, rsv, pods, quotas, chunks=1):
+def engine_run(cfg, cluster, dev, rsv, pods, quotas, chunks=1, aux_st=None):
+    """aux_st: the oracle's final state, for the comparison of the aux Requested columns (read through the Filter)."""
     with Engine(cfg, cluster.n) as e:
         synth.load_c5_into(e, cluster, dev, rsv, quotas)
         e.stage(pods)
@@ -74,12 +77,14 @@ def engine_run(cfg, cluster, dev, rsv, pods, quotas, chunks=1):
         out = dict(node=node, score=score, slot=e.fetch_reservations(0, len(pods)),
                    minors=e.fetch_devices(0, len(pods)), state=e.read_state(), rsv=e.read_reservations(),
                    dev=e.read_devices(), quotas=None if quotas is None else e.read_quotas(len(quotas)))
+        if aux_st is not None:
+            TA._assert_aux_requested_equal(e, cluster.nodes, aux_st)
     return out
 
 
-def check(cfg, cluster, dev, rsv, pods, quotas, chunks=1):
+def check(cfg, cluster, dev, rsv, pods, quotas, chunks=1, aux=False):
     w = oracle_run(cfg, cluster, dev, rsv, pods, quotas)
-    g = engine_run(cfg, cluster, dev, rsv, pods, quotas, chunks)
+    g = engine_run(cfg, cluster, dev, rsv, pods, quotas, chunks, aux_st=w["st"] if aux else None)
     bad = np.nonzero((g["node"] != w["node"]) | (g["score"] != w["score"]) | (g["slot"] != w["slot"]) |
                      (g["minors"] != w["minors"]))[0]
     assert len(bad) == 0, f"first mismatch at pod {bad[0]}: gpu " \
@@ -91,8 +96,7 @@ def check(cfg, cluster, dev, rsv, pods, quotas, chunks=1):
     assert np.array_equal(ac, np.where(on, r["allocated_cpu"], 0))
     assert np.array_equal(am, np.where(on, r["allocated_mem"], 0))
     assert np.array_equal(asg, np.where(on, r["assigned"], 0))
-    assert np.array_equal(g["state"]["requested_cpu"], w["st"]["requested"][:, abi.RES_CPU])
-    assert np.array_equal(g["state"]["num_pods"], w["st"]["num_pods"])
+    TP._assert_state_dict_equal(g["state"], w["st"])
     uc, um, ur = g["dev"]
     assert np.array_equal(uc, w["dev"]["used_core"]) and np.array_equal(um, w["dev"]["used_memory"])
     assert np.array_equal(ur, w["dev"]["used_ratio"])
@@ -108,6 +112,30 @@ def test_combined_parity(n_nodes, n_pods, seed, chunks):
     cluster, dev, rsv, pods, quotas = workload(n_nodes, n_pods, seed)
     w = check(F.build_config(profile=PROFILE), cluster, dev, rsv, pods, quotas, chunks)
     assert (w["slot"] >= 0).any() and (w["minors"] != 0).any() and (w["node"] < 0).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_pods,chunks", [(64, 1), (24, 6)], ids=["exact_rounds", "pod_per_pass"])
+def test_combined_parity_prod_and_aux_pods(n_pods, chunks):
+    """What Reserve commits, at the smallest shape that runs each exact path on 64 nodes: 64 pods in one call are two
+    exact rounds of 32 (xr_resolve's Reserve), 24 pods in calls of 4 stay below the rounds' minimum and go one pod per
+    pass (rsv_reserve).  Most of the queue is koord-prod (the prod-only LoadAware estimates move) and every second pod
+    asks ephemeral-storage or batch-cpu that only some nodes have left (the aux Requested columns move and decide
+    placements).  Beyond check()'s comparison, which covers every column of the final node state and the reservations'
+    Allocated, the aux Requested columns are compared node by node."""
+    cluster, dev, rsv, pods, quotas = workload(64, n_pods, 25)
+    rng = np.random.default_rng(26)
+    alloc = cluster.nodes["allocatable"]
+    alloc[:, abi.RES_EPHEMERAL] = rng.choice([0, 40, 100], cluster.n) * TA.GI
+    alloc[:, abi.RES_BATCH_CPU] = rng.choice([0, 4000, 8000], cluster.n)
+    pods["requests"][0::4, abi.RES_EPHEMERAL] = 30 * TA.GI
+    pods["requests"][2::4, abi.RES_BATCH_CPU] = 3000
+    prod = pods["priority_class"] == abi.PRIO_PROD
+    assert prod.any() and not prod.all()
+    w = check(F.build_config(profile=PROFILE), cluster, dev, rsv, pods, quotas, chunks, aux=True)
+    placed = w["node"] >= 0
+    assert (placed & prod).any() and (placed & (pods["requests"][:, abi.RES_EPHEMERAL] > 0)).any()
+    assert (placed & (pods["requests"][:, abi.RES_BATCH_CPU] > 0)).any() and (w["slot"] >= 0).any()
 
 
 @pytest.mark.gpu

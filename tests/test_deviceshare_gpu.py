@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import test_golden_deviceshare as TG
+import test_parity_gpu as TP
 from koordinator_amd import Engine, abi, framework, synth
 from koordinator_amd.abi import KoordGPUError
 from oracle import oracle
@@ -95,9 +96,7 @@ def _check(cfg, cluster, dev, pods, chunks=1):
     assert bad.size == 0, f"first mismatch at pod {bad[0]}: gpu ({node[bad[0]]}, {score[bad[0]]}) vs oracle " \
                           f"({want_node[bad[0]]}, {want_score[bad[0]]})"
     assert np.array_equal(minors, want_minors)
-    assert np.array_equal(state["requested_cpu"], st["requested"][:, abi.RES_CPU])
-    assert np.array_equal(state["requested_mem"], st["requested"][:, abi.RES_MEMORY])
-    assert np.array_equal(state["num_pods"], st["num_pods"])
+    TP._assert_state_dict_equal(state, st)
     assert np.array_equal(used[0], d["used_core"]) and np.array_equal(used[1], d["used_memory"])
     assert np.array_equal(used[2], d["used_ratio"])
     return node

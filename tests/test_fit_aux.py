@@ -15,6 +15,7 @@ pod does not request is not a key of its request map and is not compared."""
 import numpy as np
 import pytest
 
+import test_parity_gpu as TP
 from koordinator_amd import Engine, abi, framework as F, synth
 from oracle import oracle
 
@@ -57,6 +58,23 @@ def _state_from_pods(n, cfg, cluster):
     st = oracle.states(n)
     oracle.add_pods(cfg, st, cluster.existing_pods, cluster.existing_node)
     return st
+
+
+def _assert_aux_requested_equal(e, nodes, st, every=1):
+    """The engine's Requested of the kAux resources equals the oracle's `st` on every `every`-th node.  The columns are
+    read through the Filter: for a resource and a free amount f the oracle holds on some node, a probe asking f fits
+    exactly where the device's free amount is >= f, and one asking f + 1 where it is > f, so equal verdicts over both
+    probes of every such f pin each node's device value to the oracle's."""
+    idx = np.arange(0, len(nodes), every)
+    for r in AUX:
+        free = nodes["allocatable"][idx, r] - st["requested"][idx, r]
+        for v in sorted({int(x) for f in free for x in (f, f + 1) if x > 0} | {1}):
+            q = np.zeros(1, dtype=abi.POD_DTYPE)
+            q["requests"][0, r] = v
+            rej, _, _ = e.evaluate(q)
+            want = np.array([oracle.fit_filter(nodes[i:i + 1], st[i:i + 1], q) for i in idx])
+            np.testing.assert_array_equal(rej[idx] & abi.REJECT_FIT_OTHER, want & abi.REJECT_FIT_OTHER,
+                                          err_msg=f"resource {r}, request {v}")
 
 
 # ---- CPU: the oracle's comparison --------------------------------------------------------------------------------
@@ -160,6 +178,9 @@ def test_gpu_aux_unreserve_and_remove():
         gn2 = e.schedule(pods[1000:])[0]
         on2, _ = oracle.schedule(cfg, cl.nodes, cl.metrics, rm, pods[1000:], cl.now_ns, 4)
         np.testing.assert_array_equal(gn2, on2)
+        # the final state: what Unreserve took off every row (the prod-only estimates and the aux Requested too)
+        TP._assert_state_equal(e, rm)
+        _assert_aux_requested_equal(e, cl.nodes, rm, every=8)
 
 
 def _overcommit_case():

@@ -20,7 +20,12 @@ def _engine(cfg, cluster, capacity=None):
 
 
 def _assert_state_equal(e, st):
-    s = e.read_state()
+    _assert_state_dict_equal(e.read_state(), st)
+
+
+def _assert_state_dict_equal(s, st):
+    """Every mutable column a placement moves on the node's row (Engine.read_state()) against the oracle's state: the
+    prod-only LoadAware estimates too, which no score of the default profiles reads back."""
     np.testing.assert_array_equal(s["requested_cpu"], st["requested"][:, abi.RES_CPU])
     np.testing.assert_array_equal(s["requested_mem"], st["requested"][:, abi.RES_MEMORY])
     np.testing.assert_array_equal(s["nonzero_cpu"], st["nonzero"][:, 0])

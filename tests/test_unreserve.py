@@ -11,6 +11,7 @@ NUMA / GPU / reservation / quota state); and expiry re-evaluated when the clock 
 import numpy as np
 import pytest
 
+import test_parity_gpu as TP
 from koordinator_amd import Engine, abi, framework as F, synth
 from oracle import oracle
 
@@ -113,9 +114,7 @@ def test_unreserve_fit_loadaware_quota_interleaved():
         e.schedule_staged(a, b - a)
         g2, gs2 = e.fetch(a, b - a)
         assert np.array_equal(g2, w2) and np.array_equal(gs2, ws2)
-        s = e.read_state()
-        assert np.array_equal(s["requested_cpu"], st["requested"][:, abi.RES_CPU])
-        assert np.array_equal(s["num_pods"], st["num_pods"])
+        TP._assert_state_equal(e, st)
         assert np.array_equal(e.read_quotas(len(quotas)), q)
 
 
@@ -147,7 +146,7 @@ def test_unreserve_numa_interleaved():
         ga, gc, gm = e.read_numa()
         wa, wc, wm = oracle.numa_state_read(buf, cluster.n)
         assert np.array_equal(ga, wa) and np.array_equal(gc, wc) and np.array_equal(gm, wm)
-        assert np.array_equal(e.read_state()["requested_cpu"], st["requested"][:, abi.RES_CPU])
+        TP._assert_state_equal(e, st)
 
 
 @pytest.mark.gpu
@@ -186,6 +185,7 @@ def test_unreserve_c5_interleaved():
         assert np.array_equal(am, np.where(on, r["allocated_mem"], 0))
         assert np.array_equal(asg, np.where(on, r["assigned"], 0))
         assert np.array_equal(e.read_quotas(len(quotas)), q)
+        TP._assert_state_equal(e, st)
 
 
 @pytest.mark.gpu
