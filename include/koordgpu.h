@@ -188,7 +188,7 @@ typedef struct kg_config {
   int64_t la_prod_usage_thresholds[KG_RES_MAX];
   int64_t la_estimated_scaling_factors[KG_RES_MAX];
   int64_t la_score_according_prod_usage;       /* bool                                                */
-  /* NodeResourcesFit (upstream) LeastAllocated scoring strategy resources */
+  /* NodeResourcesFit (upstream) ScoringStrategy.Resources weights; the strategy type is fit_scoring_strategy below */
   int64_t fit_resource_weights[KG_RES_MAX];
   /* profile: plugins enabled at the Filter / Score extension points and their Score weights */
   int64_t fit_filter;                          /* NodeResourcesFit at Filter                          */
@@ -259,7 +259,14 @@ typedef struct kg_config {
   /* (ABI 17) DeviceShareArgs.ScoringStrategy.Resources weights of koordinator.sh/rdma and koordinator.sh/fpga (the
    * scorer of the RDMA / FPGA device types; v1beta2 default 1 each) */
   int64_t ds_scoring_weights_x[2];
-  int64_t reserved[1];
+  /* (within ABI 18: the former reserved word, same offset) NodeResourcesFitArgs.ScoringStrategy.Type: KG_STRATEGY_*.
+   * 0 = LeastAllocated, every earlier caller's behaviour.  MostAllocated is upstream's mostResourceScorer: per resource
+   * (cpu, memory; weight and allocatable both non-zero) q = min(NonZeroRequested + request, allocatable) * 100 /
+   * allocatable (an over-committed row scores 100), score = sum(q * w) / sum(w), both truncating.  It runs on the
+   * single-rank Fit + LoadAware round engine; kg_engine_create refuses it (KG_E_UNSUPPORTED) together with
+   * NodeNUMAResource, DeviceShare, Reservation, any upstream default plugin or several ranks.  Any other value is
+   * KG_E_INVALID (RequestedToCapacityRatio is not accelerated). */
+  int64_t fit_scoring_strategy;
 } kg_config;
 enum { KG_MULTI_RANK_AUTO = 0, KG_MULTI_RANK_SHARD = 1, KG_MULTI_RANK_REPLICA = 2 };
 
@@ -806,6 +813,13 @@ int kg_debug_least_requested(kg_engine* e, const int64_t* requested, const int64
  * that routine's exact domain; the engine sends such rows to the exact path). */
 int kg_debug_fast_lrs(kg_engine* e, const int64_t* requested, const int64_t* capacity, int64_t* out_cpu,
                       int64_t* out_mem, int64_t n);
+
+/* Debug: mostRequestedScore ((min(requested, capacity) * 100) / capacity) on n pairs, three ways: out_ref = the
+ * reference-shaped routine of the exact paths (any input), out_cpu / out_mem = the wide pass's division-free 32-bit
+ * cpu-term and f64 memory-term routines on the free term capacity - requested (-1 where the pair lies outside that
+ * routine's exact domain, the same domain as kg_debug_fast_lrs). */
+int kg_debug_fast_mrs(kg_engine* e, const int64_t* requested, const int64_t* capacity, int64_t* out_ref,
+                      int64_t* out_cpu, int64_t* out_mem, int64_t n);
 
 /* Debug: the device topology-manager policy merge — Policy.Merge + canAdmitPodResult over ≤ 2 filtered provider lists
  * (frameworkext/topologymanager/policy.go:127-185 mergeFilteredHints, policy_best_effort.go:43-48,

@@ -121,7 +121,7 @@ CONFIG_DTYPE = np.dtype([
     _i64("image_score"), _i64("weight_image"),
     _i64("spread_filter"), _i64("spread_score"), _i64("weight_spread"),
     _i64("interpod_filter"), _i64("interpod_score"), _i64("weight_interpod"), _i64("hard_pod_affinity_weight"),
-    _i64("multi_rank_mode"), _i64("ds_scoring_weights_x", 2), _i64("reserved", 1),
+    _i64("multi_rank_mode"), _i64("ds_scoring_weights_x", 2), _i64("fit_scoring_strategy"),
 ])
 
 NODE_DTYPE = np.dtype([
@@ -255,7 +255,7 @@ EXPORTED_SYMBOLS = (
     "kg_pods_stage", "kg_pods_schedule_staged", "kg_results_fetch", "kg_engine_num_nodes",
     "kg_nodes_read_state", "kg_bench_kernel", "kg_debug_least_requested", "kg_last_error", "kg_abi_version",
     "kg_abi_struct_size", "kg_nccl_unique_id", "kg_debug_rccl_selftest", "kg_debug_eval_paths", "kg_debug_stamps",
-    "kg_debug_fast_lrs",
+    "kg_debug_fast_lrs", "kg_debug_fast_mrs",
     "kg_nodes_numa_upsert", "kg_nodes_read_numa", "kg_results_fetch_cpusets", "kg_pods_evaluate_numa",
     "kg_nodes_device_upsert", "kg_nodes_read_device", "kg_results_fetch_devices", "kg_pods_evaluate_device",
     "kg_results_fetch_devices_x", "kg_nodes_read_device_x",
@@ -339,6 +339,7 @@ def load_library(path: str | None = None):
         "kg_debug_resolve": (i, [vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp, vp]),
         "kg_debug_stamps": (i, [vp, vp]),
         "kg_debug_fast_lrs": (i, [vp, vp, vp, vp, vp, i64]),
+        "kg_debug_fast_mrs": (i, [vp, vp, vp, vp, vp, vp, i64]),
         "kg_nodes_numa_upsert": (i, [vp, vp, vp, i64]),
         "kg_nodes_read_numa": (i, [vp, vp, vp, vp]),
         "kg_results_fetch_cpusets": (i, [vp, i64, i64, vp]),

@@ -336,7 +336,7 @@ __device__ __forceinline__ void group_select_write(const uint32_t (&x)[NV], uint
 // A tile holding a row outside eval_hot's exact domain: the reference-shaped int64 path for every pod (rare).
 // The row index is laundered inside the loop so the compiler cannot hoist the 19 column addresses out of it
 // (they would stay live across the wide loop and halve its occupancy).
-template <int NPT, class Sink>
+template <int NPT, int MOST, class Sink>
 __device__ __forceinline__ void eval_tile_exact(const DevTable& T, const DevPod* __restrict__ pods, int64_t first,
                                              int p0, int p1, int tile, int64_t node_base, int64_t n_local,
                                              const EvalParams& P, const Sink& sink,
@@ -353,7 +353,7 @@ __device__ __forceinline__ void eval_tile_exact(const DevTable& T, const DevPod*
       int64_t local = (int64_t)tile * (kWave * NPT) + j * kWave + lane;
       asm volatile("" : "+v"(local));
       int64_t t = 0;
-      v[j] = (local < n_local && eval_node(load_row(T, node_base + local), p, P, t)) ? (uint32_t)t + 1u : 0u;
+      v[j] = (local < n_local && eval_node<MOST>(load_row(T, node_base + local), p, P, t)) ? (uint32_t)t + 1u : 0u;
       if (P.fit_filter && (p.flags & P_AUX) && v[j] && !aux_fits(T, node_base + local, paux + (size_t)(first + pi) * kAux))
         v[j] = 0;
     }
@@ -395,7 +395,7 @@ __device__ __forceinline__ void eval_tile(const DevTable& T, const DevPod* __res
   KG_STAMP(0, 1);
   // a row outside eval_hot's exact domain anywhere in the tile: the whole tile takes the exact path
   if (__ballot(rare)) {
-    eval_tile_exact<NPT>(T, pods, first, p0, p1, tile, node_base, n_local, P, sink, paux);
+    eval_tile_exact<NPT, (PF & PF_FIT_MOST) ? 1 : 0>(T, pods, first, p0, p1, tile, node_base, n_local, P, sink, paux);
     return;
   }
   for (int pi = p0; pi < p1; ++pi) {
@@ -1046,7 +1046,7 @@ __device__ __forceinline__ uint64_t mod_key(const EvalRow& er, uint32_t node, co
     EvalParams Pr;
     __builtin_memcpy(&Pr, q, sizeof(Pr));
     int64_t t64 = 0;
-    ok = eval_node(row_of(er), p, Pr, t64);
+    ok = eval_node<(PF & PF_FIT_MOST) ? 1 : 0>(row_of(er), p, Pr, t64);
     t = (uint32_t)t64;
   }
   return ok ? make_key(t, node) : 0;
@@ -1351,7 +1351,11 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
       diag = (uint32_t)pos << 8;
       KG_POD_SUB(j, 0);
       bool from_mod = false;
-      if (nM > 0 && pos > 0) {  // a modified node is listed above e: re-score the modified rows exactly
+      // a modified node is listed above e: re-score the modified rows exactly.  MostAllocated (PF_FIT_MOST): an assume
+      // raises the winner's key, so a modified row may beat e wherever it is listed, or unlisted — every pod re-scores
+      // every modified row
+      constexpr bool kMost = (PF & PF_FIT_MOST) != 0;
+      if (nM > 0 && (kMost || pos > 0)) {
         if (!QUOTA) p = s_pods[j];
         ++n_slow;
         diag |= 1;
@@ -1367,7 +1371,7 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
         // at most its listed key / ub (monotone profile), so it cannot beat e (≥ ub).  The ≤ kBank1Probe modified
         // keys above e are matched against bank 1's nodes (past that, both banks as before).
         bool need1 = nM > kWave;
-        if (need1 && pos <= kBank1Probe) {
+        if (!kMost && need1 && pos <= kBank1Probe) {
           uint64_t hit = 0;
           for (int q = 0; q < pos; ++q) hit |= __ballot(R1.node == key_node(readlane_u64(key, q)));
           need1 = hit != 0;
@@ -1454,7 +1458,7 @@ __device__ __forceinline__ bool eval_node_numa(const Row& r, const NumaView& nv,
                                                const EvalParams& P, const NumaParams& NP, int64_t& total,
                                                NumaHint& aff) {
   int64_t t = 0;
-  if (!eval_node(r, p, P, t)) return false;
+  if (!eval_node<0>(r, p, P, t)) return false;  // (LeastAllocated: engine_create refuses MostAllocated with this plugin)
   int64_t sc = 0;
   if (!numa_eval(nv, np, NP, r.req_cpu, r.req_mem, r.alloc_cpu, r.alloc_mem, sc, aff)) return false;
   total = t + (NP.score ? sc * NP.weight : 0);
@@ -1500,7 +1504,7 @@ __global__ __launch_bounds__(kWave* kEvalWaves) void eval_round_numa(DevTable T,
     for (int pi = p0; pi < p1; ++pi) {
       const DevPod p = pods[first + pi];
       int64_t t = 0;
-      s_v[pi - p0][j][lane] = (in && eval_node(row, p, P, t)) ? (uint32_t)t + 1u : 0u;
+      s_v[pi - p0][j][lane] = (in && eval_node<0>(row, p, P, t)) ? (uint32_t)t + 1u : 0u;
     }
     rq_c = row.req_cpu;
     rq_m = row.req_mem;
@@ -2144,7 +2148,7 @@ __global__ __launch_bounds__(kWave* kEvalWaves) void ds_max_round(DevTable T, Ds
       const DevPod& pod = pods[first + p0 + k];
       bool ok;
       if (rare) {
-        ok = eval_node(row, pod, P, t);
+        ok = eval_node<0>(row, pod, P, t);  // (DeviceShare profiles: LeastAllocated Fit only)
       } else {
         uint32_t t32 = 0;
         ok = eval_hot<PF>(h, pod, P, t32);
@@ -2355,7 +2359,7 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
       if (lane < nM) {
         if (sharded) {
           int64_t t0 = 0, raw0 = 0;
-          pk = (eval_node(s_r0[lane], p, P, t0) && ds_eval(s_d0[lane], dp, DP, raw0)) ? (uint32_t)raw0 + 1u : 0u;
+          pk = (eval_node<0>(s_r0[lane], p, P, t0) && ds_eval(s_d0[lane], dp, DP, raw0)) ? (uint32_t)raw0 + 1u : 0u;
         } else {
           pk = dsval[(size_t)j * dsval_stride + midx];
         }
@@ -2364,7 +2368,7 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
       const int64_t rraw = (int64_t)((pk - 1u) & 255u);
       const uint32_t lost = (uint32_t)__popcll(__ballot(rf && (uint32_t)rraw + 1u == Mrs));
       if (most || lost >= Crs) {
-        if (lane < nM) cf = eval_node(mrow, p, P, ct) && ds_eval(s_dc[lane], dp, DP, craw);
+        if (lane < nM) cf = eval_node<0>(mrow, p, P, ct) && ds_eval(s_dc[lane], dp, DP, craw);
         have_cur = true;
         const uint32_t cm = wave_max_u32(cf ? (uint32_t)craw + 1u : 0u);
         // the normalization changed: every key of the round's lists is stale
@@ -2378,7 +2382,7 @@ __global__ __launch_bounds__(kWave) void resolve_round_ds(DevTable T, DsTable DT
     // With M_j = the round-start M every plugin term is monotone (an assume only lowers a node's key), so a
     // modified row can only beat the best unmodified candidate when that is not the pod's overall top key.
     if (nM > 0 && (pos != 0 || most)) {
-      if (!have_cur && lane < nM) cf = eval_node(mrow, p, P, ct) && ds_eval(s_dc[lane], dp, DP, craw);
+      if (!have_cur && lane < nM) cf = eval_node<0>(mrow, p, P, ct) && ds_eval(s_dc[lane], dp, DP, craw);
       const uint64_t mk = cf ? make_key(ct + (DP.score ? DP.weight * ds_normalized(craw, Mj) : 0), midx) : 0;
       const uint64_t mbest = wave_max_key(mk);
       best = mbest > best ? mbest : best;
@@ -2705,7 +2709,7 @@ __device__ uint32_t pre_node_filter(const DevTable& T, const PreNode& S, int64_t
   int64_t t = 0;
   Row r = S.r;
   r.flags &= ~F_EPH_OVER;  // recomputed below from the victim-free Requested
-  (void)eval_node(r, p, P, t, &rej);  // NodeResourcesFit + LoadAware Filter verdicts
+  (void)eval_node<0>(r, p, P, t, &rej);  // NodeResourcesFit + LoadAware Filter verdicts (the total is not used)
   bool any_aux = false;
 #pragma unroll
   for (int q = 0; q < kAux; ++q) any_aux |= rq[q] != 0;
@@ -2904,7 +2908,9 @@ __global__ void scatter_dsx(DsXNode* __restrict__ dst, const DsXNode* __restrict
   dst[idx[k]] = s[k];
 }
 
-// kg_pods_evaluate: one pod, every node, per-plugin outputs.
+// kg_pods_evaluate: one pod, every node, per-plugin outputs.  MOST: the NodeResourcesFit strategy (the host picks the
+// instantiation from kg_config.fit_scoring_strategy, so the LeastAllocated kernel is the one it always was)
+template <bool MOST>
 __global__ void evaluate_pod(DevTable T, const DevPod* __restrict__ pod, int64_t n, EvalParams P,
                              int32_t* __restrict__ reject, int64_t* __restrict__ fit, int64_t* __restrict__ la,
                              const int64_t* __restrict__ aux_req) {
@@ -2913,7 +2919,7 @@ __global__ void evaluate_pod(DevTable T, const DevPod* __restrict__ pod, int64_t
   const Row r = load_row(T, i);
   int64_t t = 0, fs = 0, ls = 0;
   uint32_t rej = 0;
-  eval_node(r, *pod, P, t, &rej, &fs, &ls);
+  eval_node<MOST ? 1 : 0>(r, *pod, P, t, &rej, &fs, &ls);
   if (P.fit_filter && (pod->flags & P_AUX) && (r.flags & F_VALID) && !aux_fits(T, i, aux_req)) rej |= 1u << 7;
   reject[i] = (int32_t)rej;
   fit[i] = fs;
@@ -3047,7 +3053,7 @@ __device__ __forceinline__ bool eval_hot_rt(const DevTable& T, int64_t i, const 
                                             uint32_t& t, bool& rare) {
   const int pf = (P.fit_filter ? PF_FIT_FILTER : 0) | (P.fit_score ? PF_FIT_SCORE : 0) |
                  (P.la_filter ? PF_LA_FILTER : 0) | (P.la_score ? PF_LA_SCORE : 0) |
-                 (P.la_score && P.la_prod_score ? PF_LA_PROD : 0);
+                 (P.la_score && P.la_prod_score ? PF_LA_PROD : 0) | (P.fit_score && P.fit_most ? PF_FIT_MOST : 0);
   switch (pf) {
 #define KG_CASE(X)                                   \
   case X: {                                          \
@@ -3058,6 +3064,8 @@ __device__ __forceinline__ bool eval_hot_rt(const DevTable& T, int64_t i, const 
     KG_CASE(0) KG_CASE(1) KG_CASE(2) KG_CASE(3) KG_CASE(4) KG_CASE(5) KG_CASE(6) KG_CASE(7)
     KG_CASE(8) KG_CASE(9) KG_CASE(10) KG_CASE(11) KG_CASE(12) KG_CASE(13) KG_CASE(14) KG_CASE(15)
     KG_CASE(24) KG_CASE(25) KG_CASE(26) KG_CASE(27) KG_CASE(28) KG_CASE(29) KG_CASE(30) KG_CASE(31)
+    KG_CASE(34) KG_CASE(35) KG_CASE(38) KG_CASE(39) KG_CASE(42) KG_CASE(43) KG_CASE(46) KG_CASE(47)
+    KG_CASE(58) KG_CASE(59) KG_CASE(62) KG_CASE(63)
 #undef KG_CASE
   }
   return false;
@@ -3066,13 +3074,15 @@ __device__ __forceinline__ bool eval_hot_rt(const DevTable& T, int64_t i, const 
 __device__ __forceinline__ bool eval_fast_rt(const EvalRow& n, const DevPod& p, const EvalParams& P, uint32_t& t,
                                              bool& rare) {
   const int pf = (P.fit_filter ? PF_FIT_FILTER : 0) | (P.fit_score ? PF_FIT_SCORE : 0) |
-                 (P.la_filter ? PF_LA_FILTER : 0) | (P.la_score ? PF_LA_SCORE : 0);
+                 (P.la_filter ? PF_LA_FILTER : 0) | (P.la_score ? PF_LA_SCORE : 0) |
+                 (P.fit_score && P.fit_most ? PF_FIT_MOST : 0);
   switch (pf) {
 #define KG_CASE(X) \
   case X:          \
     return eval_fast<X>(n, p, P, t, rare);
     KG_CASE(0) KG_CASE(1) KG_CASE(2) KG_CASE(3) KG_CASE(4) KG_CASE(5) KG_CASE(6) KG_CASE(7)
     KG_CASE(8) KG_CASE(9) KG_CASE(10) KG_CASE(11) KG_CASE(12) KG_CASE(13) KG_CASE(14) KG_CASE(15)
+    KG_CASE(34) KG_CASE(35) KG_CASE(38) KG_CASE(39) KG_CASE(42) KG_CASE(43) KG_CASE(46) KG_CASE(47)
 #undef KG_CASE
   }
   return false;
@@ -3141,6 +3151,25 @@ __global__ void debug_fast_lrs(const int64_t* req, const int64_t* cap, int64_t* 
   out_cpu[i] = cpu_dom(c, fr) ? lrs_cpu((int32_t)fr, (int32_t)c, inv100_f32(c)) : -1;
   if (mem_dom(c, fr)) {
     const int32_t a = lrs_mem((double)fr, (double)c, inv100_f64(c)), b = lrs_mem((double)fr, (double)c, invd);
+    out_mem[i] = a == b ? a : -2;
+  } else {
+    out_mem[i] = -1;
+  }
+}
+
+// kg_debug_fast_mrs: the MostAllocated quotient three ways — most_requested64 (reference-shaped, any input) and the
+// wide pass's mrs_cpu / mrs_mem on the free term capacity − requested (−1 outside the routine's exact domain; memory
+// with both reciprocal estimates, −2 flags a disagreement, as debug_fast_lrs)
+__global__ void debug_fast_mrs(const int64_t* req, const int64_t* cap, int64_t* out_ref, int64_t* out_cpu,
+                               int64_t* out_mem, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = cap[i], fr = c - req[i];
+  out_ref[i] = most_requested64(req[i], c);
+  const double invd = c > 0 ? 100.0 / (double)c : 0.0;
+  out_cpu[i] = cpu_dom(c, fr) ? mrs_cpu((int32_t)fr, (int32_t)c, inv100_f32(c)) : -1;
+  if (mem_dom(c, fr)) {
+    const int32_t a = mrs_mem((double)fr, (double)c, inv100_f64(c)), b = mrs_mem((double)fr, (double)c, invd);
     out_mem[i] = a == b ? a : -2;
   } else {
     out_mem[i] = -1;
@@ -3543,6 +3572,9 @@ int validate_config(const kg_config* c) {
   if (c->weight_fit < 0 || c->weight_fit > 1000000 || c->weight_loadaware < 0 || c->weight_loadaware > 1000000)
     return fail(KG_E_INVALID, "plugin weight out of range");
   if (c->batch_pods < 0 || c->batch_pods > kMaxB) return fail(KG_E_INVALID, "batch_pods must be in [1,%d]", kMaxB);
+  if (c->fit_scoring_strategy != KG_STRATEGY_LEAST_ALLOCATED && c->fit_scoring_strategy != KG_STRATEGY_MOST_ALLOCATED)
+    return fail(KG_E_INVALID, "NodeResourcesFit scoring strategy %lld: LeastAllocated (0) / MostAllocated (1)",
+                (long long)c->fit_scoring_strategy);
   if (c->la_agg_usage_type < KG_AGG_NONE || c->la_agg_usage_type > KG_AGG_P99 || c->la_agg_score_type < KG_AGG_NONE ||
       c->la_agg_score_type > KG_AGG_P99 || c->la_agg_usage_duration_ns < 0 || c->la_agg_score_duration_ns < 0)
     return fail(KG_E_INVALID, "LoadAwareSchedulingArgs.Aggregated: aggregation type / duration");
@@ -4303,7 +4335,11 @@ RoundGeom geometry(const kg_engine* e) {
   const bool numa_rounds = e->numa_on && !e->ds_on && !e->rsv_on;
   if (numa_rounds)
     while (d > 1 && d * g.B >= kWave) --d;
-  g.depth = (e->P.monotone || numa_rounds) ? d : 1;
+  // MostAllocated Fit on the round engine is not monotone either, and pipelines for the NUMA rounds' reason: its
+  // resolver re-scores every row modified since the snapshot for every pod, and a torn read can only be of such a row
+  // (DESIGN.md §3.24); depth · B ≤ kMaxMod above bounds its slots as it does the monotone profiles'
+  const bool most_rounds = e->P.fit_score && e->P.fit_most && !e->numa_on && !e->ds_on && !e->rsv_on;
+  g.depth = (e->P.monotone || numa_rounds || most_rounds) ? d : 1;
   if (e->numa_on) g.ppw = std::min(g.ppw, kNumaPpw);  // eval_round_numa parks ≤ kNumaPpw pods' values in LDS
   if (e->ds_on) g.ppw = std::min(g.ppw, kDsPpw);      // the DeviceShare passes keep ≤ kDsPpw pods in registers
   return g;
@@ -4322,15 +4358,29 @@ dim3 eval_grid(const RoundGeom& g, int nb) {
 
 int profile_bits(const EvalParams& P) {
   return (P.fit_filter ? PF_FIT_FILTER : 0) | (P.fit_score ? PF_FIT_SCORE : 0) | (P.la_filter ? PF_LA_FILTER : 0) |
-         (P.la_score ? PF_LA_SCORE : 0) | (P.la_score && P.la_prod_score ? PF_LA_PROD : 0);
+         (P.la_score ? PF_LA_SCORE : 0) | (P.la_score && P.la_prod_score ? PF_LA_PROD : 0) |
+         (P.fit_score && P.fit_most ? PF_FIT_MOST : 0);
 }
 
-#ifdef KG_DEV_PF  // iteration builds only (make dev): one profile instantiated; engine_create refuses every other one
+// PF_FIT_MOST (32) is legal only with PF_FIT_SCORE (2): the 8 Fit-scoring profiles of 0..15 and the 4 of 24..31, + 32.
+#ifdef KG_DEV_PF  // iteration builds only (make dev): one profile (any legal one, the + 32 ones included) instantiated;
+                  // engine_create refuses every other one
 #define KG_PF_SWITCH(pf, CALL) \
   if ((pf) == KG_DEV_PF) {     \
     CALL(KG_DEV_PF);           \
   }
+#define KG_PF_SWITCH_LEAST(pf, CALL) KG_PF_SWITCH(pf, CALL)
 #else
+// the profiles without PF_FIT_MOST: what the kernels of profiles that refuse MostAllocated (DeviceShare) instantiate
+#define KG_PF_SWITCH_LEAST(pf, CALL)                                                             \
+  switch (pf) {                                                                                \
+    case 0: CALL(0); break;   case 1: CALL(1); break;   case 2: CALL(2); break;   case 3: CALL(3); break;     \
+    case 4: CALL(4); break;   case 5: CALL(5); break;   case 6: CALL(6); break;   case 7: CALL(7); break;     \
+    case 8: CALL(8); break;   case 9: CALL(9); break;   case 10: CALL(10); break; case 11: CALL(11); break;   \
+    case 12: CALL(12); break; case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break;   \
+    case 24: CALL(24); break; case 25: CALL(25); break; case 26: CALL(26); break; case 27: CALL(27); break;   \
+    case 28: CALL(28); break; case 29: CALL(29); break; case 30: CALL(30); break; case 31: CALL(31); break;   \
+  }
 #define KG_PF_SWITCH(pf, CALL)                                                                   \
   switch (pf) {                                                                                \
     case 0: CALL(0); break;   case 1: CALL(1); break;   case 2: CALL(2); break;   case 3: CALL(3); break;     \
@@ -4339,6 +4389,9 @@ int profile_bits(const EvalParams& P) {
     case 12: CALL(12); break; case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break;   \
     case 24: CALL(24); break; case 25: CALL(25); break; case 26: CALL(26); break; case 27: CALL(27); break;   \
     case 28: CALL(28); break; case 29: CALL(29); break; case 30: CALL(30); break; case 31: CALL(31); break;   \
+    case 34: CALL(34); break; case 35: CALL(35); break; case 38: CALL(38); break; case 39: CALL(39); break;   \
+    case 42: CALL(42); break; case 43: CALL(43); break; case 46: CALL(46); break; case 47: CALL(47); break;   \
+    case 58: CALL(58); break; case 59: CALL(59); break; case 62: CALL(62); break; case 63: CALL(63); break;   \
   }
 #endif
 
@@ -4591,7 +4644,7 @@ int launch_round_ds(kg_engine* e, const RoundGeom& g, int64_t end, hipStream_t s
   ds_max_round<X><<<grid, kWave * kEvalWaves, 0, st>>>(e->T, DT, e->pods.p, e->dpods.p, e->cursor.p, end, g.B, g.ppw, \
                                                        g.base, g.n_local, g.nt_local, e->P, e->DP, e->dsmax.p,     \
                                                        e->dsval.p)
-    KG_PF_SWITCH(profile_bits(e->P), KG_DSMAX)
+    KG_PF_SWITCH_LEAST(profile_bits(e->P), KG_DSMAX)
 #undef KG_DSMAX
     prof_end(e, KG_PROF_DS_MAX, t, st);
   }
@@ -5306,6 +5359,21 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
   // rank holds the same placements.
   if (c.multi_rank_mode < KG_MULTI_RANK_AUTO || c.multi_rank_mode > KG_MULTI_RANK_REPLICA)
     return bail(fail(KG_E_INVALID, "multi_rank_mode %lld", (long long)c.multi_rank_mode));
+  // NodeResourcesFit MostAllocated runs on the single-rank Fit + LoadAware round engine only: the other resolvers and
+  // the exact rounds rest on terms that only move down, and the sharded resolver sees a part of the table
+  // 
+  if (c.fit_scoring_strategy == KG_STRATEGY_MOST_ALLOCATED) {
+    const char* with = e->numa_on  ? "NodeNUMAResource"
+                       : e->ds_on  ? "DeviceShare"
+                       : e->rsv_on ? "Reservation"
+                       : e->def_on ? "the upstream default plugins (TaintToleration / NodeAffinity / "
+                                     "NodeResourcesBalancedAllocation / ImageLocality / PodTopologySpread / InterPodAffinity)"
+                       : n_ranks > 1 ? "an engine of several ranks"
+                                     : nullptr;
+    if (with)
+      return bail(fail(KG_E_UNSUPPORTED, "NodeResourcesFit MostAllocated together with %s keeps the Go path (its resolver "
+                                         "is exact for the Fit + LoadAware round engine on one rank only)", with));
+  }
   if (n_ranks > 1) {
     const bool heavy_exact = e->exact_on && !e->grp_on && (e->numa_on || e->ds_on);
     const bool shard = c.multi_rank_mode == KG_MULTI_RANK_SHARD ||
@@ -5398,6 +5466,9 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
   e->P.score_bits = (int32_t)bits_for(max_total);
   // NodeResourcesFit + LoadAwareScheduling: assume only lowers a node's key; NodeNUMAResource does not
   e->P.monotone = (e->numa_on || e->ds_on || e->rsv_on) ? 0 : 1;  // DeviceShare: normalization couples every node's key
+  // NodeResourcesFit MostAllocated: an assume raises the winner's Fit score
+  e->P.fit_most = (int32_t)(c.fit_scoring_strategy == KG_STRATEGY_MOST_ALLOCATED);
+  if (e->P.fit_most && e->P.fit_score) e->P.monotone = 0;
   e->DP.filter = (int32_t)(c.ds_filter != 0);
   e->DP.score = (int32_t)(c.ds_score != 0);
   e->DP.weight = (int32_t)c.weight_deviceshare;
@@ -6184,8 +6255,13 @@ int kg_pods_evaluate(kg_engine* e, const kg_pod* pod, int32_t* out_reject, int64
   HIP_TRY(hipMemcpyAsync(s_pod.at(b), &d, sizeof(d), hipMemcpyHostToDevice, e->stream));
   if (int rc = e->paux1.ensure(kAux)) return rc;
   HIP_TRY(hipMemcpyAsync(e->paux1.p, &pod->requests[kAuxFirst], kAux * 8, hipMemcpyHostToDevice, e->stream));
-  evaluate_pod<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(e->T, s_pod.at(b), n, e->P, e->scratch32.p, s_fit.at(b),
-                                                                   s_la.at(b), e->paux1.p);
+  const unsigned eval_blocks = (unsigned)((n + 255) / 256);
+  if (e->P.fit_most)
+    evaluate_pod<true><<<eval_blocks, 256, 0, e->stream>>>(e->T, s_pod.at(b), n, e->P, e->scratch32.p, s_fit.at(b),
+                                                           s_la.at(b), e->paux1.p);
+  else
+    evaluate_pod<false><<<eval_blocks, 256, 0, e->stream>>>(e->T, s_pod.at(b), n, e->P, e->scratch32.p, s_fit.at(b),
+                                                            s_la.at(b), e->paux1.p);
   HIP_TRY(hipGetLastError());
   std::vector<int32_t> rej(n);
   std::vector<int64_t> fs(n), ls(n);
@@ -6924,6 +7000,24 @@ int kg_debug_fast_lrs(kg_engine* e, const int64_t* req, const int64_t* cap, int6
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_cpu, b.p + 2 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(out_mem, b.p + 3 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  b.release();
+  return 0;
+}
+
+int kg_debug_fast_mrs(kg_engine* e, const int64_t* req, const int64_t* cap, int64_t* out_ref, int64_t* out_cpu,
+                      int64_t* out_mem, int64_t n) {
+  if (!e || n < 0 || (n > 0 && (!req || !cap || !out_ref || !out_cpu || !out_mem))) return fail(KG_E_INVALID, "bad argument");
+  if (n == 0) return 0;
+  DevBuf<int64_t> b;
+  if (int rc = b.ensure(5 * n)) return rc;
+  HIP_TRY(hipMemcpyAsync(b.p, req, n * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b.p + n, cap, n * 8, hipMemcpyHostToDevice, e->stream));
+  debug_fast_mrs<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(b.p, b.p + n, b.p + 2 * n, b.p + 3 * n, b.p + 4 * n, n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_ref, b.p + 2 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_cpu, b.p + 3 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_mem, b.p + 4 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   b.release();
   return 0;

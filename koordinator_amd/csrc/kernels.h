@@ -6,6 +6,7 @@
 //   upstream NodeResourcesFit.Filter (fitsRequest)       — restated in-tree: reservation/plugin.go:433-482
 //   LoadAwareScheduling.Filter                            — load_aware.go:123-171 (threshold verdict precomputed)
 //   upstream NodeResourcesFit.Score (LeastAllocated, NonZeroRequested) — nodenumaresource/scoring.go:191-230
+//     (or MostAllocated, kg_config.fit_scoring_strategy: upstream's mostResourceScorer)
 //   LoadAwareScheduling.Score                             — load_aware.go:269-335, scorer :378-397
 //   weighted sum over plugins                             — upstream RunScorePlugins (framework_extender.go:236-258)
 // eval_fast<PF>() is the same function on hoisted per-node terms, specialised at compile time on the profile
@@ -77,6 +78,9 @@ __device__ unsigned long long g_lane_diag[64][8];
 // profile bits (compile-time specialisation of the evaluation kernels)
 constexpr int PF_FIT_FILTER = 1, PF_FIT_SCORE = 2, PF_LA_FILTER = 4, PF_LA_SCORE = 8;
 constexpr int PF_LA_PROD = 16;  // LoadAware ScoreAccordingProdUsage: prod pods score on the prod-usage terms
+// NodeResourcesFit ScoringStrategy MostAllocated (legal only with PF_FIT_SCORE): the Fit terms are mrs_*, and the
+// resolver drops its monotone shortcuts (an assume RAISES the winner's key)
+constexpr int PF_FIT_MOST = 32;
 
 // node flags (device)
 constexpr uint32_t F_VALID = 1u << 0;
@@ -150,7 +154,7 @@ struct EvalParams {
   float inv_fit_ws[4];  // 1 / Σ fit weights, indexed by (alloc_cpu != 0) | (alloc_mem != 0) << 1
   int32_t fit_wsum32;   // Σ fit weights (cpu + memory)
   int32_t la_prod_score;  // LoadAwareSchedulingArgs.ScoreAccordingProdUsage
-  int32_t pad3;
+  int32_t fit_most;       // NodeResourcesFitArgs.ScoringStrategy.Type == MostAllocated (kg_config.fit_scoring_strategy)
 };
 
 struct Row {
@@ -240,6 +244,11 @@ __device__ __forceinline__ int64_t div_small(int64_t s, int64_t w) {
 
 // Reference-shaped fused Filter + Score of one node for one pod (runtime profile).  Returns false when any
 // enabled Filter rejects the node; otherwise writes the weighted total Σ_p weight_p · score_p.
+// MOST: the NodeResourcesFit strategy where the caller knows it at compile time (1 = MostAllocated, 0 = LeastAllocated:
+// the kernels specialised on the profile bits), -1 = P.fit_most at run time.  MostAllocated is upstream's
+// mostResourceScorer: per resource (min(NonZeroRequested + request, allocatable) · 100) / allocatable — an
+// over-committed row scores 100 where LeastAllocated scores 0 — then the same weighted mean.
+template <int MOST = -1>
 __device__ __forceinline__ bool eval_node(const Row& n, const DevPod& p, const EvalParams& P, int64_t& total,
                                           uint32_t* reject = nullptr, int64_t* fit_out = nullptr,
                                           int64_t* la_out = nullptr) {
@@ -262,12 +271,15 @@ __device__ __forceinline__ bool eval_node(const Row& n, const DevPod& p, const E
   int64_t t = 0, fs = 0, ls = 0;
   if (P.fit_score || fit_out) {
     int64_t s = 0, ws = 0;
+    const bool most = MOST < 0 ? P.fit_most != 0 : MOST != 0;
     if (P.fit_w_cpu && n.alloc_cpu != 0) {
-      s += least_requested(n.nz_cpu + p.nz_cpu, n.alloc_cpu) * P.fit_w_cpu;
+      const int64_t rc = n.nz_cpu + p.nz_cpu;
+      s += (most ? most_requested64(rc, n.alloc_cpu) : least_requested(rc, n.alloc_cpu)) * P.fit_w_cpu;
       ws += P.fit_w_cpu;
     }
     if (P.fit_w_mem && n.alloc_mem != 0) {
-      s += least_requested(n.nz_mem + p.nz_mem, n.alloc_mem) * P.fit_w_mem;
+      const int64_t rm = n.nz_mem + p.nz_mem;
+      s += (most ? most_requested64(rm, n.alloc_mem) : least_requested(rm, n.alloc_mem)) * P.fit_w_mem;
       ws += P.fit_w_mem;
     }
     fs = ws ? div_small(s, ws) : 0;
@@ -489,6 +501,17 @@ __device__ __forceinline__ int32_t lrs_mem(double x, double cap, double inv) {
   return q;
 }
 
+// mostRequestedScore ((min(requested, capacity) · 100) / capacity) on the fast path, from the same free term x =
+// capacity − requested: min(requested, capacity) = capacity − max(x, 0), which inside the domain (x ≤ capacity) lies in
+// [0, capacity] — the range lrs_* is exact on — so it is the same estimate-and-correct routine on that value.  x < 0
+// (over-committed) gives capacity, i.e. 100.
+__device__ __forceinline__ int32_t mrs_cpu(int32_t x, int32_t cap, float inv) {
+  return lrs_cpu(cap - (x < 0 ? 0 : x), cap, inv);
+}
+__device__ __forceinline__ int32_t mrs_mem(double x, double cap, double inv) {
+  return lrs_mem(cap - __builtin_fmax(x, 0.0), cap, inv);
+}
+
 // s / w for 0 ≤ s ≤ 100·w, w ≤ 2·10⁶ (validate_config): f32 estimate + one correction step, 24-bit multiplies.
 __device__ __forceinline__ int32_t div_est(int32_t s, int32_t w, float inv_w) {
   int q = (int)((float)s * inv_w);
@@ -532,8 +555,14 @@ __device__ __forceinline__ bool eval_fast(const EvalRow& n, const DevPod& p, con
   uint32_t t = 0;
   if constexpr ((PF & (PF_FIT_SCORE | PF_LA_SCORE)) != 0) rare |= (n.flags & F_RARE) != 0;
   if constexpr ((PF & PF_FIT_SCORE) != 0) {
-    const int32_t qc = lrs_cpu((int32_t)n.fnz_cpu - p.nz_cpu32, (int32_t)n.alloc_cpu, n.inv_cpu);
-    const int32_t qm = lrs_mem(n.fnz_mem - p.nz_mem_d, n.alloc_mem, n.inv_mem);
+    int32_t qc, qm;
+    if constexpr ((PF & PF_FIT_MOST) != 0) {
+      qc = mrs_cpu((int32_t)n.fnz_cpu - p.nz_cpu32, (int32_t)n.alloc_cpu, n.inv_cpu);
+      qm = mrs_mem(n.fnz_mem - p.nz_mem_d, n.alloc_mem, n.inv_mem);
+    } else {
+      qc = lrs_cpu((int32_t)n.fnz_cpu - p.nz_cpu32, (int32_t)n.alloc_cpu, n.inv_cpu);
+      qm = lrs_mem(n.fnz_mem - p.nz_mem_d, n.alloc_mem, n.inv_mem);
+    }
     const int32_t s = (int32_t)(__umul24((uint32_t)qc, (uint32_t)P.fit_w_cpu) +
                                 __umul24((uint32_t)qm, (uint32_t)P.fit_w_mem));
     const int32_t f = div_est(s, n.fit_ws, n.inv_fit_ws);
@@ -699,8 +728,14 @@ __device__ __forceinline__ bool eval_hot(const HotRow& n, const DevPod& p, const
   }
   uint32_t t = 0;
   if constexpr ((PF & PF_FIT_SCORE) != 0) {
-    const int32_t qc = lrs_cpu(n.fnz_cpu - p.nz_cpu32, n.alloc_cpu, n.inv_cpu);
-    const int32_t qm = lrs_mem(n.fnz_mem - p.nz_mem_d, n.alloc_mem, n.inv_mem);
+    int32_t qc, qm;
+    if constexpr ((PF & PF_FIT_MOST) != 0) {
+      qc = mrs_cpu(n.fnz_cpu - p.nz_cpu32, n.alloc_cpu, n.inv_cpu);
+      qm = mrs_mem(n.fnz_mem - p.nz_mem_d, n.alloc_mem, n.inv_mem);
+    } else {
+      qc = lrs_cpu(n.fnz_cpu - p.nz_cpu32, n.alloc_cpu, n.inv_cpu);
+      qm = lrs_mem(n.fnz_mem - p.nz_mem_d, n.alloc_mem, n.inv_mem);
+    }
     const int32_t s = (int32_t)(__umul24((uint32_t)qc, (uint32_t)P.fit_w_cpu) +
                                 __umul24((uint32_t)qm, (uint32_t)P.fit_w_mem));
     // inside the domain every weighted resource has allocatable > 0: Σ weights is the profile constant

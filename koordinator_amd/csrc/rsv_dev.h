@@ -400,7 +400,9 @@ __device__ __forceinline__ uint32_t rsv_status(uint32_t fl) {
 // reserve-pod / operating-mode / reservation-selector logic (the batched exact rounds; the host routes queues holding
 // such pods to the per-pod pass); kXF = false: no RDMA / FPGA evaluation and no reserved-cpus NodeNUMAResource Score
 // (the host picks it when the queue holds no RDMA / FPGA request and no reservation holds cpus: fewer registers)
-template <bool kSlotsInRegs = true, bool kExt = true, bool kXF = true, bool kNuma = true, bool kDs = true>
+// kMost: eval_node's MOST (0 = LeastAllocated at compile time: the profiles that refuse NodeResourcesFit MostAllocated;
+// -1 = EvalParams.fit_most at run time: the per-pod pass of the Fit + LoadAware profiles and the debug / diagnose hooks)
+template <bool kSlotsInRegs = true, bool kExt = true, bool kXF = true, bool kNuma = true, bool kDs = true, int kMost = -1>
 __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode* __restrict__ RN,
                                                 const int32_t* __restrict__ rsv_n, int64_t i, const DevPod& p,
                                                 const RsvPod& rp, const EvalParams& P, const RsvParams& RP,
@@ -469,15 +471,15 @@ __device__ __forceinline__ RsvOut rsv_eval_node(const DevTable& T, const RsvNode
   int64_t t = 0;
   if (st) {  // every NodeResourcesFit reason and LoadAware's, as kg_pods_evaluate reports them
     uint32_t rej = 0;
-    eval_node(r, p, P, t, &rej);
+    eval_node<kMost>(r, p, P, t, &rej);
     fl |= rej;
   } else if (dbg) {  // the same call with the two plugins' Scores reported
     int64_t fs = 0, ls = 0;
-    const bool ok = eval_node(r, p, P, t, nullptr, &fs, &ls);
+    const bool ok = eval_node<kMost>(r, p, P, t, nullptr, &fs, &ls);
     dbg->w_fit = P.fit_score ? fs * P.weight_fit : 0;
     dbg->w_la = P.la_score ? ls * P.weight_la : 0;
     if (!ok) return o;
-  } else if (!eval_node(r, p, P, t)) return o;  // NodeResourcesFit + LoadAware on the restored NodeInfo
+  } else if (!eval_node<kMost>(r, p, P, t)) return o;  // NodeResourcesFit + LoadAware on the restored NodeInfo
   // fitsRequest over ephemeral-storage and the scalar resources the pod requests (reservation/plugin.go:469-479)
   if (aux_req && P.fit_filter && !aux_fits(T, i, aux_req)) {
     if (!st) return o;
@@ -1107,7 +1109,8 @@ __global__ __launch_bounds__(kRsvThreads) void rsv_eval(DevTable T, RsvNode* __r
     const NumaPod* np = X.ns ? &X.npods[j] : nullptr;
     const int64_t* aux = (X.paux && (p.flags & P_AUX)) ? X.paux + (size_t)j * kAux : nullptr;
     const DefPod* df = X.defp ? &X.defp[j] : nullptr;
-    RsvOut o = rsv_eval_node<true, true, (F & RSV_F_XF) != 0, (F & RSV_F_NUMA) != 0, (F & RSV_F_DS) != 0>(
+    RsvOut o = rsv_eval_node<true, true, (F & RSV_F_XF) != 0, (F & RSV_F_NUMA) != 0, (F & RSV_F_DS) != 0,
+                             (F & (RSV_F_NUMA | RSV_F_DS)) != 0 ? 0 : -1>(
         T, RN, rsv_n, i, p, rp, P, RP, X, dp, np, nullptr, aux, df);
     // nominated pods: before rsv_pack and the block partials below, so the NormalizeScore maxima are the narrowed set's
     if (o.feas && X.nom) {

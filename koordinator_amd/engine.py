@@ -752,3 +752,14 @@ class Engine:
         check(self.lib, self.lib.kg_debug_fast_lrs(self.h, ptr(requested), ptr(capacity), ptr(oc), ptr(om),
                                                    len(requested)))
         return oc, om
+
+    def debug_fast_mrs(self, requested, capacity):
+        """(reference-shaped, cpu-routine, memory-routine) mostRequestedScore; a fast routine gives -1 outside its domain."""
+        requested = np.ascontiguousarray(requested, dtype=np.int64)
+        capacity = np.ascontiguousarray(capacity, dtype=np.int64)
+        ref = np.zeros(len(requested), dtype=np.int64)
+        oc = np.zeros(len(requested), dtype=np.int64)
+        om = np.zeros(len(requested), dtype=np.int64)
+        check(self.lib, self.lib.kg_debug_fast_mrs(self.h, ptr(requested), ptr(capacity), ptr(ref), ptr(oc), ptr(om),
+                                                   len(requested)))
+        return ref, oc, om

@@ -134,7 +134,9 @@ class LoadAwareSchedulingArgs:
 
 @dataclass
 class NodeResourcesFitArgs:
+    """Upstream NodeResourcesFitArgs.ScoringStrategy: Type (LeastAllocated / MostAllocated) and Resources weights."""
     scoring_resources: dict = field(default_factory=lambda: {"cpu": 1, "memory": 1})
+    scoring_strategy: str = "LeastAllocated"
 
 
 @dataclass
@@ -194,6 +196,11 @@ def build_config(la: LoadAwareSchedulingArgs | None = None, fit: NodeResourcesFi
     r["la_agg_score_type"] = abi.AGG_TYPES[agg.get("score_type", "")]
     r["la_agg_score_duration_ns"] = int(agg.get("score_duration_s", 0) * 10**9)
     r["fit_resource_weights"] = _slots(fit.scoring_resources)
+    if fit.scoring_strategy not in abi.STRATEGY:
+        # RequestedToCapacityRatio (its shape function) is not accelerated: such a profile keeps the Go path
+        raise ValueError(f"NodeResourcesFitArgs.ScoringStrategy.Type {fit.scoring_strategy!r}: the engine scores "
+                         f"{' / '.join(abi.STRATEGY)}")
+    r["fit_scoring_strategy"] = abi.STRATEGY[fit.scoring_strategy]
     r["fit_filter"] = int(NODE_RESOURCES_FIT in profile.filter)
     r["la_filter"] = int(LOAD_AWARE in profile.filter)
     r["fit_score"] = int(NODE_RESOURCES_FIT in profile.score)
