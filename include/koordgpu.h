@@ -47,6 +47,10 @@
  *   kg_nominated_pods_set   the nominator (upstream PodNominator: AddNominatedPod / DeleteNominatedPodIfExists), resident on the
  *                           device; kg_pods_schedule_staged_nominated and the resident preemption calls then filter as
  *                           RunFilterPluginsWithNominatedPods does (framework_extender.go:204-258 wraps it).
+ *   kg_fit_shape_set        NodeResourcesFitArgs.ScoringStrategy.Type = RequestedToCapacityRatio with its
+ *                           RequestedToCapacityRatio.Shape (upstream v1.24 requestedToCapacityRatioScorer +
+ *                           BuildBrokenLinearFunction; the reference tree does not carry it): switches the engine's
+ *                           NodeResourcesFit Score to the shape, or back to the configured strategy.
  *   kg_last_error           error text for the last failing call on this thread (maps to framework.NewStatus(Error,…)).
  *
  * Units follow the reference's getResourceValue (load_aware/helper.go:146-151): cpu-like resources in
@@ -265,7 +269,8 @@ typedef struct kg_config {
    * allocatable (an over-committed row scores 100), score = sum(q * w) / sum(w), both truncating.  It runs on the
    * single-rank Fit + LoadAware round engine; kg_engine_create refuses it (KG_E_UNSUPPORTED) together with
    * NodeNUMAResource, DeviceShare, Reservation, any upstream default plugin or several ranks.  Any other value is
-   * KG_E_INVALID (RequestedToCapacityRatio is not accelerated). */
+   * KG_E_INVALID.  RequestedToCapacityRatio has no value here (the struct has no room for its shape): create the engine
+   * with 0 and hand the shape to kg_fit_shape_set. */
   int64_t fit_scoring_strategy;
 } kg_config;
 enum { KG_MULTI_RANK_AUTO = 0, KG_MULTI_RANK_SHARD = 1, KG_MULTI_RANK_REPLICA = 2 };
@@ -820,6 +825,33 @@ int kg_debug_fast_lrs(kg_engine* e, const int64_t* requested, const int64_t* cap
  * routine's exact domain, the same domain as kg_debug_fast_lrs). */
 int kg_debug_fast_mrs(kg_engine* e, const int64_t* requested, const int64_t* capacity, int64_t* out_ref,
                       int64_t* out_cpu, int64_t* out_mem, int64_t n);
+
+/* (within ABI 18) NodeResourcesFit RequestedToCapacityRatio.  A shape is n >= 1 points (utilization, score):
+ * utilization strictly increasing within [0, 100], score within [0, 10] (used as score * 10).  raw(p) is upstream's
+ * broken-linear function: the first point's score up to its utilization, the last point's past it, and in between
+ * S[i-1] + (S[i] - S[i-1]) * (p - U[i-1]) / (U[i] - U[i-1]) with int64 division truncating toward zero.  Per resource
+ * (cpu, memory; weight and allocatable both non-zero) r = raw(u), u = MostAllocated's quotient (requested > capacity ?
+ * 100 : requested * 100 / capacity, requested = NonZeroRequested + the pod's non-zero request); the node's score is
+ * round-half-away(sum(r * w) / sum(w)) over the resources with r > 0, and 0 when there is none.
+ *
+ * kg_fit_shape_set switches the engine's NodeResourcesFit Score to that rule; n = 0 returns to the configured strategy.
+ * Legal between any two calls, like an informer delta.  KG_E_INVALID: n > 101, a malformed point, or an engine created
+ * with fit_scoring_strategy = MostAllocated.  KG_E_UNSUPPORTED (the message names the reason): NodeNUMAResource,
+ * DeviceShare, Reservation, any upstream default plugin or several ranks (replicas included) - what MostAllocated
+ * refuses at create.  A refused call changes nothing.  With fit_score off the shape is accepted and has no effect. */
+typedef struct kg_shape_point {
+  int64_t utilization;
+  int64_t score;
+} kg_shape_point;
+int kg_fit_shape_set(kg_engine* e, const kg_shape_point* points, int64_t n);
+/* The table raw(0..100) the engine scores with (101 values, all 0 when no shape is set) and whether
+ * RequestedToCapacityRatio is active; either pointer may be NULL. */
+int kg_fit_shape_get(kg_engine* e, int64_t* out_lut101, int64_t* out_active);
+/* Debug: the per-resource score raw(u) of n (requested, capacity) pairs three ways, as kg_debug_fast_mrs gives u:
+ * out_ref through the reference-shaped routine (any input), out_cpu / out_mem through the wide pass's routines (-1
+ * where the pair lies outside that routine's exact domain). */
+int kg_debug_fit_shape(kg_engine* e, const int64_t* requested, const int64_t* capacity, int64_t* out_ref,
+                       int64_t* out_cpu, int64_t* out_mem, int64_t n);
 
 /* Debug: the device topology-manager policy merge — Policy.Merge + canAdmitPodResult over ≤ 2 filtered provider lists
  * (frameworkext/topologymanager/policy.go:127-185 mergeFilteredHints, policy_best_effort.go:43-48,

@@ -220,6 +220,10 @@ TOPN_MAX = 64  # KG_TOPN_MAX
 PL_FIT, PL_LOADAWARE, PL_NUMA, PL_DEVICESHARE, PL_RESERVATION, PL_TAINT, PL_NODE_AFFINITY, PL_BALANCED, \
     PL_IMAGE_LOCALITY = range(9)
 PL_COLUMNS = 16  # KG_PL_COLUMNS
+# kg_shape_point: one point of NodeResourcesFit's RequestedToCapacityRatio shape (kg_fit_shape_set)
+SHAPE_POINT_DTYPE = np.dtype([_i64("utilization"), _i64("score")])
+FIT_SHAPE_MAX_POINTS = 101
+
 TOPN_ROW_DTYPE = np.dtype([("node_idx", np.int32), ("nominated", np.int32), _i64("total"), _i64("plugin", PL_COLUMNS)])
 
 # (added within ABI 18) kg_pods_diagnose: one pod's framework.FitError counts.  plugin_nodes[KG_PL_*] = the nodes whose
@@ -255,7 +259,7 @@ EXPORTED_SYMBOLS = (
     "kg_pods_stage", "kg_pods_schedule_staged", "kg_results_fetch", "kg_engine_num_nodes",
     "kg_nodes_read_state", "kg_bench_kernel", "kg_debug_least_requested", "kg_last_error", "kg_abi_version",
     "kg_abi_struct_size", "kg_nccl_unique_id", "kg_debug_rccl_selftest", "kg_debug_eval_paths", "kg_debug_stamps",
-    "kg_debug_fast_lrs", "kg_debug_fast_mrs",
+    "kg_debug_fast_lrs", "kg_debug_fast_mrs", "kg_fit_shape_set", "kg_fit_shape_get", "kg_debug_fit_shape",
     "kg_nodes_numa_upsert", "kg_nodes_read_numa", "kg_results_fetch_cpusets", "kg_pods_evaluate_numa",
     "kg_nodes_device_upsert", "kg_nodes_read_device", "kg_results_fetch_devices", "kg_pods_evaluate_device",
     "kg_results_fetch_devices_x", "kg_nodes_read_device_x",
@@ -340,6 +344,9 @@ def load_library(path: str | None = None):
         "kg_debug_stamps": (i, [vp, vp]),
         "kg_debug_fast_lrs": (i, [vp, vp, vp, vp, vp, i64]),
         "kg_debug_fast_mrs": (i, [vp, vp, vp, vp, vp, vp, i64]),
+        "kg_fit_shape_set": (i, [vp, vp, i64]),
+        "kg_fit_shape_get": (i, [vp, vp, vp]),
+        "kg_debug_fit_shape": (i, [vp, vp, vp, vp, vp, vp, i64]),
         "kg_nodes_numa_upsert": (i, [vp, vp, vp, i64]),
         "kg_nodes_read_numa": (i, [vp, vp, vp, vp]),
         "kg_results_fetch_cpusets": (i, [vp, i64, i64, vp]),

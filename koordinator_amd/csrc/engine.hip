@@ -365,7 +365,8 @@ __device__ __forceinline__ void eval_tile_exact(const DevTable& T, const DevPod*
 template <int PF, int NPT, bool AUX, class Sink>
 __device__ __forceinline__ void eval_tile(const DevTable& T, const DevPod* __restrict__ pods, int64_t first, int p0,
                                           int p1, int tile, int64_t node_base, int64_t n_local, const EvalParams& P,
-                                          const Sink& sink, const int64_t* __restrict__ paux, int lane) {
+                                          const Sink& sink, const int64_t* __restrict__ paux, int lane,
+                                          const uint8_t* lut) {
 
   HotRow rows[NPT];
   uint32_t gidx[NPT];
@@ -395,7 +396,7 @@ __device__ __forceinline__ void eval_tile(const DevTable& T, const DevPod* __res
   KG_STAMP(0, 1);
   // a row outside eval_hot's exact domain anywhere in the tile: the whole tile takes the exact path
   if (__ballot(rare)) {
-    eval_tile_exact<NPT, (PF & PF_FIT_MOST) ? 1 : 0>(T, pods, first, p0, p1, tile, node_base, n_local, P, sink, paux);
+    eval_tile_exact<NPT, fit_strategy_of(PF)>(T, pods, first, p0, p1, tile, node_base, n_local, P, sink, paux);
     return;
   }
   for (int pi = p0; pi < p1; ++pi) {
@@ -404,7 +405,7 @@ __device__ __forceinline__ void eval_tile(const DevTable& T, const DevPod* __res
 #pragma unroll
     for (int j = 0; j < NPT; ++j) {
       uint32_t t = 0;
-      v[j] = eval_hot<PF>(rows[j], p, P, t) ? t + 1u : 0u;
+      v[j] = eval_hot<PF>(rows[j], p, P, t, lut) ? t + 1u : 0u;
     }
     // ephemeral-storage / scalar requests: the Allocatable-Requested columns.  (r5) Compiled only into the AUX
     // instantiation (a staged queue holding such a pod): the check cost the common kernel 20 VGPRs
@@ -457,14 +458,26 @@ __global__ __launch_bounds__(kWave* kEW) KG_EVAL_ATTR void eval_round(DevTable T
   // the tile top-kR lists to LDS instead and combines them.  A shard of fewer than kCombineTiles tiles keeps one list
   // per tile: a pod's record needs kC candidates.
   extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
-  const EvalLds L = eval_lds(kEW, kETile, kRG, pods_per_wave, combine != 0);
+  constexpr bool kShape = (PF & PF_FIT_RTCR) != 0;
+  const EvalLds L = eval_lds(kEW, kETile, kRG, pods_per_wave, combine != 0, kShape);
   uint64_t* const s_lists = lds_at<uint64_t>(smem, L.lists);  // [kEW][pods_per_wave][kR] (the tile lists to combine)
+  // RequestedToCapacityRatio (PF_FIT_RTCR): the block's copy of the shape table, kFitLutBytes bytes filled once — 16
+  // bytes by each of its first 8 threads — before the barrier every thread of the block reaches (the returns above are
+  // block-uniform).  eval_hot reads it per (pod, node) with clamped byte indices (fit_lut_at).
+  const uint8_t* s_lut = nullptr;
+  if constexpr (kShape) {
+    static_assert(kFitLutBytes % 16 == 0 && kFitLutBytes / 16 <= kWave * kEW, "one uint4 per thread");
+    uint4* const dst = lds_at<uint4>(smem, L.lut);
+    if (threadIdx.x < kFitLutBytes / 16) dst[threadIdx.x] = reinterpret_cast<const uint4*>(P.fit_lut)[threadIdx.x];
+    __syncthreads();
+    s_lut = lds_at<const uint8_t>(smem, L.lut);
+  }
   const int ng_local = (nt_local + kEW - 1) / kEW, grp = tile0 / kEW;
   if (!combine) {
     if (tile < nt_local)
       eval_tile<PF, kENPT, AUX>(T, pods, first, p0, p1, tile, node_base, n_local, P,
                                 TileListSink{lists + ((size_t)p0 * nt_local + tile) * kR, (int64_t)nt_local * kR, vbits},
-                                paux, lane);
+                                paux, lane, s_lut);
     return;
   }
   if (L.staged) {
@@ -473,7 +486,7 @@ __global__ __launch_bounds__(kWave* kEW) KG_EVAL_ATTR void eval_round(DevTable T
     uint32_t* const my_v = vals + wave * kETile;
     if (tile < nt_local) {
       eval_tile<PF, kENPT, AUX>(T, pods, first, p0, p1, tile, node_base, n_local, P, TileStageSink{my_v, kPodVals}, paux,
-                                lane);
+                                lane, s_lut);
     } else {  // a tile past the shard: no node, no value
       for (int pl = 0; pl < p1 - p0; ++pl)
 #pragma unroll
@@ -504,7 +517,7 @@ __global__ __launch_bounds__(kWave* kEW) KG_EVAL_ATTR void eval_round(DevTable T
     uint64_t* my_l = s_lists + (size_t)wave * pods_per_wave * kR;
     if (tile < nt_local)
       eval_tile<PF, kENPT, AUX>(T, pods, first, p0, p1, tile, node_base, n_local, P, TileListSink{my_l, kR, vbits}, paux,
-                                lane);
+                                lane, s_lut);
     else
       for (int q = lane; q < (p1 - p0) * kR; q += kWave) my_l[q] = 0;
     __syncthreads();
@@ -1036,17 +1049,17 @@ __global__ __launch_bounds__(kWave * 4) void merge_wave(DevTable T, EvalParams P
 // resolver's scalar registers.
 template <int PF>
 __device__ __forceinline__ uint64_t mod_key(const EvalRow& er, uint32_t node, const DevPod& p, const EvalParams& P,
-                                            const uint64_t* s_par) {
+                                            const uint64_t* s_par, const uint8_t* lut) {
   uint32_t t = 0;
   bool rare = false;
-  bool ok = eval_fast<PF>(er, p, P, t, rare);
+  bool ok = eval_fast<PF>(er, p, P, t, rare, lut);
   if (rare) {
     const uint64_t* q = s_par;
     asm volatile("" : "+v"(q));
     EvalParams Pr;
     __builtin_memcpy(&Pr, q, sizeof(Pr));
     int64_t t64 = 0;
-    ok = eval_node<(PF & PF_FIT_MOST) ? 1 : 0>(row_of(er), p, Pr, t64);
+    ok = eval_node<fit_strategy_of(PF)>(row_of(er), p, Pr, t64);
     t = (uint32_t)t64;
   }
   return ok ? make_key(t, node) : 0;
@@ -1079,8 +1092,8 @@ __device__ __forceinline__ void mod_row_init(ModRow& m) {
 }
 template <int PF>
 __device__ __forceinline__ uint64_t mod_row_key(const ModRow& m, const DevPod& p, const EvalParams& P,
-                                                const uint64_t* s_par) {
-  return m.node == kNoNode ? 0 : mod_key<PF>(m.er, m.node, p, P, s_par);
+                                                const uint64_t* s_par, const uint8_t* lut) {
+  return m.node == kNoNode ? 0 : mod_key<PF>(m.er, m.node, p, P, s_par, lut);
 }
 
 // assume(pod) on a modified row (NodeInfo.AddPod + LoadAware Reserve → podAssignCache.assign): only the free terms
@@ -1234,7 +1247,8 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
   const int lane = threadIdx.x;
   // the serial chain outranks the wide pass's waves when they share a SIMD
   __builtin_amdgcn_s_setprio(3);
-  const ResolveLds L = resolve_lds(nb, bitmap_words);
+  constexpr bool kShape = (PF & PF_FIT_RTCR) != 0;
+  const ResolveLds L = resolve_lds(nb, bitmap_words, kShape);
   uint64_t* s_cand = lds_at<uint64_t>(smem, L.cand);
   uint64_t* s_podw = lds_at<uint64_t>(smem, L.pods);
   uint64_t* s_par = lds_at<uint64_t>(smem, L.par);
@@ -1247,6 +1261,13 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
 #pragma unroll
     for (int q = 0; q < kParWords; ++q)
       if (lane == q) s_par[q] = pw[q];
+  }
+  // RequestedToCapacityRatio (PF_FIT_RTCR): the shape table's kFitLutBytes bytes, 16 per lane of the first 8, visible to
+  // the wave after the prologue's barriers; mod_key reads it with clamped byte indices (fit_lut_at)
+  const uint8_t* s_lut = nullptr;
+  if constexpr (kShape) {
+    if (lane < kFitLutBytes / 16) lds_at<uint4>(smem, L.lut)[lane] = reinterpret_cast<const uint4*>(P.fit_lut)[lane];
+    s_lut = lds_at<const uint8_t>(smem, L.lut);
   }
   {  // prologue, independent of the previous round: LDS-DMA of this round's records (merged on this stream)
      // + pods, bitmap / hash clears (16-B stores)
@@ -1353,8 +1374,9 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
       bool from_mod = false;
       // a modified node is listed above e: re-score the modified rows exactly.  MostAllocated (PF_FIT_MOST): an assume
       // raises the winner's key, so a modified row may beat e wherever it is listed, or unlisted — every pod re-scores
-      // every modified row
-      constexpr bool kMost = (PF & PF_FIT_MOST) != 0;
+      // every modified row.  RequestedToCapacityRatio (PF_FIT_RTCR) is not monotone for any shape and
+      // takes the same rule (§3.25)
+      constexpr bool kMost = (PF & (PF_FIT_MOST | PF_FIT_RTCR)) != 0;
       if (nM > 0 && (kMost || pos > 0)) {
         if (!QUOTA) p = s_pods[j];
         ++n_slow;
@@ -1363,7 +1385,7 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
         const int64_t* rq = paux + (size_t)(first + j) * kAux;
         mod_row_settle<PF>(R0, s_cand, s_pods, T0, P);
         if (lane == 0) KG_LANE_SUB(j, 0);
-        uint64_t mk = mod_row_key<PF>(R0, p, P, s_par);
+        uint64_t mk = mod_row_key<PF>(R0, p, P, s_par, s_lut);
         if (lane == 0) KG_LANE_SUB(j, 1);
         if (aux && mk && !mod_aux_fits(table_at(T0), R0.node, rq, j, my_out, s_pods, paux + (size_t)first * kAux))
           mk = 0;
@@ -1378,7 +1400,7 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
         }
         if (need1) {
           mod_row_settle<PF>(R1, s_cand, s_pods, T0, P);
-          uint64_t k1 = mod_row_key<PF>(R1, p, P, s_par);
+          uint64_t k1 = mod_row_key<PF>(R1, p, P, s_par, s_lut);
           if (aux && k1 && !mod_aux_fits(table_at(T0), R1.node, rq, j, my_out, s_pods, paux + (size_t)first * kAux))
             k1 = 0;
           mk = k1 > mk ? k1 : mk;
@@ -2909,8 +2931,9 @@ __global__ void scatter_dsx(DsXNode* __restrict__ dst, const DsXNode* __restrict
 }
 
 // kg_pods_evaluate: one pod, every node, per-plugin outputs.  MOST: the NodeResourcesFit strategy (the host picks the
-// instantiation from kg_config.fit_scoring_strategy, so the LeastAllocated kernel is the one it always was)
-template <bool MOST>
+// instantiation from kg_config.fit_scoring_strategy / the shape set by kg_fit_shape_set — eval_node's 0 / 1 / 2 — so
+// the LeastAllocated kernel is the one it always was)
+template <int MOST>
 __global__ void evaluate_pod(DevTable T, const DevPod* __restrict__ pod, int64_t n, EvalParams P,
                              int32_t* __restrict__ reject, int64_t* __restrict__ fit, int64_t* __restrict__ la,
                              const int64_t* __restrict__ aux_req) {
@@ -2919,7 +2942,7 @@ __global__ void evaluate_pod(DevTable T, const DevPod* __restrict__ pod, int64_t
   const Row r = load_row(T, i);
   int64_t t = 0, fs = 0, ls = 0;
   uint32_t rej = 0;
-  eval_node<MOST ? 1 : 0>(r, *pod, P, t, &rej, &fs, &ls);
+  eval_node<MOST>(r, *pod, P, t, &rej, &fs, &ls);
   if (P.fit_filter && (pod->flags & P_AUX) && (r.flags & F_VALID) && !aux_fits(T, i, aux_req)) rej |= 1u << 7;
   reject[i] = (int32_t)rej;
   fit[i] = fs;
@@ -3053,19 +3076,22 @@ __device__ __forceinline__ bool eval_hot_rt(const DevTable& T, int64_t i, const 
                                             uint32_t& t, bool& rare) {
   const int pf = (P.fit_filter ? PF_FIT_FILTER : 0) | (P.fit_score ? PF_FIT_SCORE : 0) |
                  (P.la_filter ? PF_LA_FILTER : 0) | (P.la_score ? PF_LA_SCORE : 0) |
-                 (P.la_score && P.la_prod_score ? PF_LA_PROD : 0) | (P.fit_score && P.fit_most ? PF_FIT_MOST : 0);
+                 (P.la_score && P.la_prod_score ? PF_LA_PROD : 0) | (P.fit_score && P.fit_most ? PF_FIT_MOST : 0) |
+                 (P.fit_score && P.fit_rtcr ? PF_FIT_RTCR : 0);
   switch (pf) {
 #define KG_CASE(X)                                   \
   case X: {                                          \
     const HotRow h = load_hot<X>(T, i, P);           \
     rare = (h.flags & F_RARE) != 0;                  \
-    return eval_hot<X>(h, p, P, t);                  \
+    return eval_hot<X>(h, p, P, t, P.fit_lut);       \
   }
     KG_CASE(0) KG_CASE(1) KG_CASE(2) KG_CASE(3) KG_CASE(4) KG_CASE(5) KG_CASE(6) KG_CASE(7)
     KG_CASE(8) KG_CASE(9) KG_CASE(10) KG_CASE(11) KG_CASE(12) KG_CASE(13) KG_CASE(14) KG_CASE(15)
     KG_CASE(24) KG_CASE(25) KG_CASE(26) KG_CASE(27) KG_CASE(28) KG_CASE(29) KG_CASE(30) KG_CASE(31)
     KG_CASE(34) KG_CASE(35) KG_CASE(38) KG_CASE(39) KG_CASE(42) KG_CASE(43) KG_CASE(46) KG_CASE(47)
     KG_CASE(58) KG_CASE(59) KG_CASE(62) KG_CASE(63)
+    KG_CASE(66) KG_CASE(67) KG_CASE(70) KG_CASE(71) KG_CASE(74) KG_CASE(75) KG_CASE(78) KG_CASE(79)
+    KG_CASE(90) KG_CASE(91) KG_CASE(94) KG_CASE(95)
 #undef KG_CASE
   }
   return false;
@@ -3075,14 +3101,15 @@ __device__ __forceinline__ bool eval_fast_rt(const EvalRow& n, const DevPod& p, 
                                              bool& rare) {
   const int pf = (P.fit_filter ? PF_FIT_FILTER : 0) | (P.fit_score ? PF_FIT_SCORE : 0) |
                  (P.la_filter ? PF_LA_FILTER : 0) | (P.la_score ? PF_LA_SCORE : 0) |
-                 (P.fit_score && P.fit_most ? PF_FIT_MOST : 0);
+                 (P.fit_score && P.fit_most ? PF_FIT_MOST : 0) | (P.fit_score && P.fit_rtcr ? PF_FIT_RTCR : 0);
   switch (pf) {
 #define KG_CASE(X) \
   case X:          \
-    return eval_fast<X>(n, p, P, t, rare);
+    return eval_fast<X>(n, p, P, t, rare, P.fit_lut);
     KG_CASE(0) KG_CASE(1) KG_CASE(2) KG_CASE(3) KG_CASE(4) KG_CASE(5) KG_CASE(6) KG_CASE(7)
     KG_CASE(8) KG_CASE(9) KG_CASE(10) KG_CASE(11) KG_CASE(12) KG_CASE(13) KG_CASE(14) KG_CASE(15)
     KG_CASE(34) KG_CASE(35) KG_CASE(38) KG_CASE(39) KG_CASE(42) KG_CASE(43) KG_CASE(46) KG_CASE(47)
+    KG_CASE(66) KG_CASE(67) KG_CASE(70) KG_CASE(71) KG_CASE(74) KG_CASE(75) KG_CASE(78) KG_CASE(79)
 #undef KG_CASE
   }
   return false;
@@ -3171,6 +3198,24 @@ __global__ void debug_fast_mrs(const int64_t* req, const int64_t* cap, int64_t* 
   if (mem_dom(c, fr)) {
     const int32_t a = mrs_mem((double)fr, (double)c, inv100_f64(c)), b = mrs_mem((double)fr, (double)c, invd);
     out_mem[i] = a == b ? a : -2;
+  } else {
+    out_mem[i] = -1;
+  }
+}
+
+// kg_debug_fit_shape: the RequestedToCapacityRatio per-resource score lut[u] three ways, as debug_fast_mrs gives u
+// (−1 outside a fast routine's exact domain, −2 where memory's two reciprocal estimates disagree)
+__global__ void debug_fit_shape(const uint8_t* __restrict__ lut, const int64_t* req, const int64_t* cap,
+                                int64_t* out_ref, int64_t* out_cpu, int64_t* out_mem, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = cap[i], fr = c - req[i];
+  out_ref[i] = fit_lut_at(lut, (int32_t)most_requested64(req[i], c));
+  const double invd = c > 0 ? 100.0 / (double)c : 0.0;
+  out_cpu[i] = cpu_dom(c, fr) ? fit_lut_at(lut, mrs_cpu((int32_t)fr, (int32_t)c, inv100_f32(c))) : -1;
+  if (mem_dom(c, fr)) {
+    const int32_t a = mrs_mem((double)fr, (double)c, inv100_f64(c)), b = mrs_mem((double)fr, (double)c, invd);
+    out_mem[i] = a == b ? fit_lut_at(lut, a) : -2;
   } else {
     out_mem[i] = -1;
   }
@@ -3308,6 +3353,12 @@ struct kg_engine {
   int64_t capacity = 0;
   int64_t n_nodes = 0;  // highest upserted index + 1
   EvalParams P{};
+  // RequestedToCapacityRatio (kg_fit_shape_set): the shape table lut[0..100] as the host built it, its device copy
+  // (kFitLutBytes bytes of uint8_t, zero-padded, allocated at create: P.fit_lut never changes) and the configured
+  // P.monotone, restored when the shape is cleared
+  int64_t fit_lut_host[101] = {};
+  DevBuf<uint8_t> fit_lut;
+  int32_t monotone_cfg = 0;
   // host mirror of static / ingest state
   std::vector<kg_node> nodes;
   std::vector<kg_node_metric> metrics;
@@ -4338,7 +4389,8 @@ RoundGeom geometry(const kg_engine* e) {
   // MostAllocated Fit on the round engine is not monotone either, and pipelines for the NUMA rounds' reason: its
   // resolver re-scores every row modified since the snapshot for every pod, and a torn read can only be of such a row
   // (DESIGN.md §3.24); depth · B ≤ kMaxMod above bounds its slots as it does the monotone profiles'
-  const bool most_rounds = e->P.fit_score && e->P.fit_most && !e->numa_on && !e->ds_on && !e->rsv_on;
+  // RequestedToCapacityRatio (kg_fit_shape_set) takes the same resolver rule and keeps the depth for the same reason
+  const bool most_rounds = e->P.fit_score && (e->P.fit_most || e->P.fit_rtcr) && !e->numa_on && !e->ds_on && !e->rsv_on;
   g.depth = (e->P.monotone || numa_rounds || most_rounds) ? d : 1;
   if (e->numa_on) g.ppw = std::min(g.ppw, kNumaPpw);  // eval_round_numa parks ≤ kNumaPpw pods' values in LDS
   if (e->ds_on) g.ppw = std::min(g.ppw, kDsPpw);      // the DeviceShare passes keep ≤ kDsPpw pods in registers
@@ -4359,10 +4411,12 @@ dim3 eval_grid(const RoundGeom& g, int nb) {
 int profile_bits(const EvalParams& P) {
   return (P.fit_filter ? PF_FIT_FILTER : 0) | (P.fit_score ? PF_FIT_SCORE : 0) | (P.la_filter ? PF_LA_FILTER : 0) |
          (P.la_score ? PF_LA_SCORE : 0) | (P.la_score && P.la_prod_score ? PF_LA_PROD : 0) |
-         (P.fit_score && P.fit_most ? PF_FIT_MOST : 0);
+         (P.fit_score && P.fit_most ? PF_FIT_MOST : 0) | (P.fit_score && P.fit_rtcr ? PF_FIT_RTCR : 0);
 }
 
 // PF_FIT_MOST (32) is legal only with PF_FIT_SCORE (2): the 8 Fit-scoring profiles of 0..15 and the 4 of 24..31, + 32.
+// PF_FIT_RTCR (64) likewise, and never with PF_FIT_MOST: the same 12, + 64.  Its cases come last, so that the kernels
+// they instantiate are emitted after every earlier one.
 #ifdef KG_DEV_PF  // iteration builds only (make dev): one profile (any legal one, the + 32 ones included) instantiated;
                   // engine_create refuses every other one
 #define KG_PF_SWITCH(pf, CALL) \
@@ -4392,6 +4446,9 @@ int profile_bits(const EvalParams& P) {
     case 34: CALL(34); break; case 35: CALL(35); break; case 38: CALL(38); break; case 39: CALL(39); break;   \
     case 42: CALL(42); break; case 43: CALL(43); break; case 46: CALL(46); break; case 47: CALL(47); break;   \
     case 58: CALL(58); break; case 59: CALL(59); break; case 62: CALL(62); break; case 63: CALL(63); break;   \
+    case 66: CALL(66); break; case 67: CALL(67); break; case 70: CALL(70); break; case 71: CALL(71); break;   \
+    case 74: CALL(74); break; case 75: CALL(75); break; case 78: CALL(78); break; case 79: CALL(79); break;   \
+    case 90: CALL(90); break; case 91: CALL(91); break; case 94: CALL(94); break; case 95: CALL(95); break;   \
   }
 #endif
 
@@ -4408,7 +4465,7 @@ template <int X>
 void launch_eval_round(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int slot, hipStream_t st) {
   auto go = [&](auto kern) {
     // the kernel carves its LDS with the same call (the ppw and the combine flag it is passed)
-    const uint32_t lds = eval_lds(kEW, kETile, kRG, g.ppw, eval_combine(g)).bytes();
+    const uint32_t lds = eval_lds(kEW, kETile, kRG, g.ppw, eval_combine(g), (X & PF_FIT_RTCR) != 0).bytes();
     kern<<<eval_grid_e(g, nb), kWave * kEW, lds, st>>>(e->T, e->pods.p, first, nb, g.ppw, g.base, g.n_local, g.nte, e->P,
                                                       lists_slot(e, g, slot), poison_ptr(e), e->paux.p,
                                                       eval_combine(g) ? 1 : 0);
@@ -4511,7 +4568,7 @@ void launch_resolve(kg_engine* e, const RoundGeom& g, int64_t first, int nb, int
     return;
   }
 #define KG_RESOLVE_T(X, Q)                                                                                       \
-  resolve_round<X, Q><<<1, kWave, resolve_lds(nb, g.bitmap_words).bytes(), st>>>(                                \
+  resolve_round<X, Q><<<1, kWave, resolve_lds(nb, g.bitmap_words, ((X) & PF_FIT_RTCR) != 0).bytes(), st>>>(                               \
       e->T, e->pods.p, e->cursor.p, first, nb, cand_slot(e, g, slot), e->P, e->out_keys.p, g.bitmap_words,       \
       e->modlists.p, slot, g.depth, n_prev, poison_ptr(e), seq, wait, e->quotas.p, e->nq, e->paux.p)
 #define KG_RESOLVE(X) KG_RESOLVE_T(X, false)
@@ -4704,7 +4761,7 @@ int prepare_rounds(kg_engine* e, RoundGeom& g) {
   // the LDS of a full round of the resolver these rounds launch (the two-wave NUMA resolver only runs where it fits)
   const size_t lds = e->ds_on     ? ds_lds(g.B, e->nq, e->n_ranks > 1, g.bitmap_words).bytes()
                      : e->numa_on ? numa_lds(g.B, g.bitmap_words).bytes()
-                                  : resolve_lds(g.B, g.bitmap_words).bytes();
+                                  : resolve_lds(g.B, g.bitmap_words, (profile_bits(e->P) & PF_FIT_RTCR) != 0).bytes();
   if (lds > kMaxLds)
     return fail(KG_E_UNSUPPORTED, "%sresolver LDS %zu B > %zu B: fewer nodes or a smaller batch_pods",
                 e->ds_on ? "DeviceShare " : e->numa_on ? "NodeNUMAResource " : "", lds, kMaxLds);
@@ -5469,6 +5526,10 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
   // NodeResourcesFit MostAllocated: an assume raises the winner's Fit score
   e->P.fit_most = (int32_t)(c.fit_scoring_strategy == KG_STRATEGY_MOST_ALLOCATED);
   if (e->P.fit_most && e->P.fit_score) e->P.monotone = 0;
+  e->monotone_cfg = e->P.monotone;
+  if (int rc = e->fit_lut.ensure(kFitLutBytes)) return bail(rc);
+  if (hipMemsetAsync(e->fit_lut.p, 0, kFitLutBytes, e->stream) != hipSuccess) return bail(fail(KG_E_DEVICE, "hipMemset"));
+  e->P.fit_lut = e->fit_lut.p;
   e->DP.filter = (int32_t)(c.ds_filter != 0);
   e->DP.score = (int32_t)(c.ds_score != 0);
   e->DP.weight = (int32_t)c.weight_deviceshare;
@@ -5626,6 +5687,7 @@ void kg_engine_destroy(kg_engine* e) {
   if (e->comm) ncclCommDestroy(e->comm);
   for (hipEvent_t ev : e->prof_pool) (void)hipEventDestroy(ev);
   e->cols64.release();
+  e->fit_lut.release();
   e->paux.release();
   e->paux1.release();
   e->cols32.release();
@@ -6256,11 +6318,14 @@ int kg_pods_evaluate(kg_engine* e, const kg_pod* pod, int32_t* out_reject, int64
   if (int rc = e->paux1.ensure(kAux)) return rc;
   HIP_TRY(hipMemcpyAsync(e->paux1.p, &pod->requests[kAuxFirst], kAux * 8, hipMemcpyHostToDevice, e->stream));
   const unsigned eval_blocks = (unsigned)((n + 255) / 256);
-  if (e->P.fit_most)
-    evaluate_pod<true><<<eval_blocks, 256, 0, e->stream>>>(e->T, s_pod.at(b), n, e->P, e->scratch32.p, s_fit.at(b),
-                                                           s_la.at(b), e->paux1.p);
+  if (e->P.fit_rtcr)
+    evaluate_pod<2><<<eval_blocks, 256, 0, e->stream>>>(e->T, s_pod.at(b), n, e->P, e->scratch32.p, s_fit.at(b),
+                                                        s_la.at(b), e->paux1.p);
+  else if (e->P.fit_most)
+    evaluate_pod<1><<<eval_blocks, 256, 0, e->stream>>>(e->T, s_pod.at(b), n, e->P, e->scratch32.p, s_fit.at(b),
+                                                        s_la.at(b), e->paux1.p);
   else
-    evaluate_pod<false><<<eval_blocks, 256, 0, e->stream>>>(e->T, s_pod.at(b), n, e->P, e->scratch32.p, s_fit.at(b),
+    evaluate_pod<0><<<eval_blocks, 256, 0, e->stream>>>(e->T, s_pod.at(b), n, e->P, e->scratch32.p, s_fit.at(b),
                                                             s_la.at(b), e->paux1.p);
   HIP_TRY(hipGetLastError());
   std::vector<int32_t> rej(n);
@@ -7020,6 +7085,121 @@ int kg_debug_fast_mrs(kg_engine* e, const int64_t* req, const int64_t* cap, int6
   HIP_TRY(hipMemcpyAsync(out_mem, b.p + 4 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   b.release();
+  return 0;
+}
+
+int kg_debug_fit_shape(kg_engine* e, const int64_t* req, const int64_t* cap, int64_t* out_ref, int64_t* out_cpu,
+                       int64_t* out_mem, int64_t n) {
+  if (!e || n < 0 || (n > 0 && (!req || !cap || !out_ref || !out_cpu || !out_mem))) return fail(KG_E_INVALID, "bad argument");
+  if (n == 0) return 0;
+  DevBuf<int64_t> b;
+  if (int rc = b.ensure(5 * n)) return rc;
+  HIP_TRY(hipMemcpyAsync(b.p, req, n * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b.p + n, cap, n * 8, hipMemcpyHostToDevice, e->stream));
+  debug_fit_shape<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(e->fit_lut.p, b.p, b.p + n, b.p + 2 * n, b.p + 3 * n,
+                                                                      b.p + 4 * n, n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_ref, b.p + 2 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_cpu, b.p + 3 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_mem, b.p + 4 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  b.release();
+  return 0;
+}
+
+// NodeResourcesFit RequestedToCapacityRatio: upstream's BuildBrokenLinearFunction over the shape's points, with
+// Score · (MaxNodeScore / MaxCustomPriorityScore) = Score · 10, tabulated for every integer utilization 0..100.  int64
+// `/` truncates toward zero as Go's does (the numerator is negative on a falling segment).
+static void fit_shape_table(const kg_shape_point* pt, int64_t n, int64_t* lut) {
+  for (int64_t p = 0; p <= 100; ++p) {
+    int64_t v = pt[n - 1].score * 10;
+    for (int64_t i = 0; i < n; ++i) {
+      if (p <= pt[i].utilization) {
+        if (i == 0) {
+          v = pt[0].score * 10;
+        } else {
+          const int64_t s0 = pt[i - 1].score * 10, s1 = pt[i].score * 10;
+          const int64_t u0 = pt[i - 1].utilization, u1 = pt[i].utilization;
+          v = s0 + (s1 - s0) * (p - u0) / (u1 - u0);
+        }
+        break;
+      }
+    }
+    lut[p] = v;
+  }
+}
+
+int kg_fit_shape_set(kg_engine* e, const kg_shape_point* points, int64_t n) {
+  if (!e) return fail(KG_E_INVALID, "engine is NULL");
+  if (n < 0 || n > 101 || (n > 0 && !points)) return fail(KG_E_INVALID, "shape: 0 to 101 points");
+  for (int64_t i = 0; i < n; ++i) {
+    if (points[i].utilization < 0 || points[i].utilization > 100)
+      return fail(KG_E_INVALID, "shape point %lld: utilization %lld outside [0, 100]", (long long)i, (long long)points[i].utilization);
+    if (i > 0 && points[i].utilization <= points[i - 1].utilization)
+      return fail(KG_E_INVALID, "shape point %lld: utilization must be strictly increasing", (long long)i);
+    if (points[i].score < 0 || points[i].score > 10)
+      return fail(KG_E_INVALID, "shape point %lld: score %lld outside [0, 10]", (long long)i, (long long)points[i].score);
+  }
+  if (n > 0) {
+    if (e->cfg.fit_scoring_strategy == KG_STRATEGY_MOST_ALLOCATED)
+      return fail(KG_E_INVALID, "a RequestedToCapacityRatio shape on an engine created with MostAllocated: one "
+                                "NodeResourcesFit scoring strategy at a time");
+    // the companions MostAllocated refuses at create, for its reason: the other resolvers and the exact rounds rest on
+    // terms that only move down, and the sharded resolver sees a part of the table
+    const char* with = e->numa_on  ? "NodeNUMAResource"
+                       : e->ds_on  ? "DeviceShare"
+                       : e->rsv_on ? "Reservation"
+                       : e->def_on ? "the upstream default plugins (TaintToleration / NodeAffinity / "
+                                     "NodeResourcesBalancedAllocation / ImageLocality / PodTopologySpread / InterPodAffinity)"
+                       : (e->n_ranks > 1 || e->replica_ranks > 1) ? "an engine of several ranks"
+                                                                  : nullptr;
+    if (with)
+      return fail(KG_E_UNSUPPORTED, "NodeResourcesFit RequestedToCapacityRatio together with %s keeps the Go path (its "
+                                    "resolver is exact for the Fit + LoadAware round engine on one rank only)", with);
+#ifdef KG_DEV_PF
+    if (e->P.fit_score)
+      return fail(KG_E_UNSUPPORTED, "iteration build (KG_DEV_PF=%d): the RequestedToCapacityRatio profiles are not compiled in", KG_DEV_PF);
+#endif
+  }
+  // no round may be in flight while the table and the strategy change (calls are synchronous, so this returns at once)
+  for (int k = 0; k < kMaxDepth; ++k)
+    if (e->rs[k]) HIP_TRY(hipStreamSynchronize(e->rs[k]));
+  uint8_t bytes[kFitLutBytes] = {};
+  std::memset(e->fit_lut_host, 0, sizeof(e->fit_lut_host));
+  if (n > 0) {
+    fit_shape_table(points, n, e->fit_lut_host);
+    for (int p = 0; p <= 100; ++p) bytes[p] = (uint8_t)e->fit_lut_host[p];
+  }
+  HIP_TRY(hipMemcpyAsync(e->fit_lut.p, bytes, kFitLutBytes, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));  // `bytes` is on this frame
+  // EvalParams travels by value into every kernel: the round launches read e->P per call, and the cached hipGraphs of
+  // the per-pod pass carry e->P in their signature (GraphSig), so a graph captured under the other strategy is
+  // re-captured, never replayed.  With fit_score off the shape is accepted and has no effect.
+  e->P.fit_rtcr = (int32_t)(n > 0);
+  e->P.monotone = (e->P.fit_rtcr && e->P.fit_score) ? 0 : e->monotone_cfg;
+  if (e->P.fit_rtcr && e->P.fit_score) {
+    const int lds = (int)kMaxLds;
+    hipError_t fe = hipSuccess;
+#define KG_ATTR(X)                                                                                           \
+  fe = hipFuncSetAttribute((const void*)resolve_round<X, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
+  if (fe == hipSuccess)                                                                                      \
+    fe = hipFuncSetAttribute((const void*)resolve_round<X, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)
+    KG_PF_SWITCH(profile_bits(e->P), KG_ATTR)
+#undef KG_ATTR
+    if (fe != hipSuccess) return fail(KG_E_DEVICE, "hipFuncSetAttribute(resolve_round LDS)");
+  }
+  return 0;
+}
+
+int kg_fit_shape_get(kg_engine* e, int64_t* out_lut101, int64_t* out_active) {
+  if (!e) return fail(KG_E_INVALID, "engine is NULL");
+  if (out_lut101) {  // the device copy the kernels read (equal to fit_lut_host by construction)
+    uint8_t bytes[kFitLutBytes];
+    HIP_TRY(hipMemcpyAsync(bytes, e->fit_lut.p, kFitLutBytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int p = 0; p <= 100; ++p) out_lut101[p] = bytes[p];
+  }
+  if (out_active) *out_active = e->P.fit_rtcr;
   return 0;
 }
 

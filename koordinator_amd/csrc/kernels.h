@@ -6,7 +6,8 @@
 //   upstream NodeResourcesFit.Filter (fitsRequest)       — restated in-tree: reservation/plugin.go:433-482
 //   LoadAwareScheduling.Filter                            — load_aware.go:123-171 (threshold verdict precomputed)
 //   upstream NodeResourcesFit.Score (LeastAllocated, NonZeroRequested) — nodenumaresource/scoring.go:191-230
-//     (or MostAllocated, kg_config.fit_scoring_strategy: upstream's mostResourceScorer)
+//     (or MostAllocated, kg_config.fit_scoring_strategy: upstream's mostResourceScorer, DESIGN.md §3.24;
+//      or RequestedToCapacityRatio, kg_fit_shape_set: upstream's broken-linear shape)
 //   LoadAwareScheduling.Score                             — load_aware.go:269-335, scorer :378-397
 //   weighted sum over plugins                             — upstream RunScorePlugins (framework_extender.go:236-258)
 // eval_fast<PF>() is the same function on hoisted per-node terms, specialised at compile time on the profile
@@ -81,6 +82,13 @@ constexpr int PF_LA_PROD = 16;  // LoadAware ScoreAccordingProdUsage: prod pods 
 // NodeResourcesFit ScoringStrategy MostAllocated (legal only with PF_FIT_SCORE): the Fit terms are mrs_*, and the
 // resolver drops its monotone shortcuts (an assume RAISES the winner's key)
 constexpr int PF_FIT_MOST = 32;
+// NodeResourcesFit ScoringStrategy RequestedToCapacityRatio (legal only with PF_FIT_SCORE, never with PF_FIT_MOST): the
+// Fit terms are lut[mrs_*] and the mean is rounded over the resources scoring > 0.  Not monotone for any shape, so the
+// resolver takes PF_FIT_MOST's rule
+constexpr int PF_FIT_RTCR = 64;
+// eval_node's strategy parameter of a profile: 0 LeastAllocated, 1 MostAllocated, 2 RequestedToCapacityRatio
+constexpr int fit_strategy_of(int pf) { return (pf & PF_FIT_RTCR) ? 2 : (pf & PF_FIT_MOST) ? 1 : 0; }
+constexpr int kFitLutBytes = 128;  // the shape table lut[0..100] as uint8_t, zero-padded to 128 bytes (device and LDS)
 
 // node flags (device)
 constexpr uint32_t F_VALID = 1u << 0;
@@ -155,7 +163,11 @@ struct EvalParams {
   int32_t fit_wsum32;   // Σ fit weights (cpu + memory)
   int32_t la_prod_score;  // LoadAwareSchedulingArgs.ScoreAccordingProdUsage
   int32_t fit_most;       // NodeResourcesFitArgs.ScoringStrategy.Type == MostAllocated (kg_config.fit_scoring_strategy)
+  int32_t fit_rtcr;       // ... == RequestedToCapacityRatio (kg_fit_shape_set; never together with fit_most)
+  int32_t pad4;
+  const uint8_t* fit_lut;  // the shape table in device memory: kFitLutBytes bytes at an address fixed at create
 };
+static_assert(sizeof(EvalParams) == 128, "EvalParams layout (a graph signature hashes its bytes: no implicit padding)");
 
 struct Row {
   int64_t alloc_cpu, alloc_mem, req_cpu, req_mem, nz_cpu, nz_mem;
@@ -235,6 +247,12 @@ __device__ __forceinline__ int64_t most_requested64(int64_t requested, int64_t c
   return q;
 }
 
+// The RequestedToCapacityRatio shape value of a utilization quotient: every index into the table — this one in device
+// memory, or its LDS copy — is clamped to [0, 100], so no input reads outside its kFitLutBytes bytes.
+__device__ __forceinline__ int32_t fit_lut_at(const uint8_t* lut, int32_t u) {
+  return (int32_t)lut[u < 0 ? 0 : (u > 100 ? 100 : u)];
+}
+
 // s / w for the per-plugin weight sums: 32-bit unsigned division whenever both fit (always, for validated
 // weights ≤ 1e6), exact int64 truncating division otherwise (Go semantics).
 __device__ __forceinline__ int64_t div_small(int64_t s, int64_t w) {
@@ -248,6 +266,11 @@ __device__ __forceinline__ int64_t div_small(int64_t s, int64_t w) {
 // the kernels specialised on the profile bits), -1 = P.fit_most at run time.  MostAllocated is upstream's
 // mostResourceScorer: per resource (min(NonZeroRequested + request, allocatable) · 100) / allocatable — an
 // over-committed row scores 100 where LeastAllocated scores 0 — then the same weighted mean.
+// 2 = RequestedToCapacityRatio (run time: P.fit_rtcr): per resource r = lut[that quotient]; s = Σ r·w and ws = Σ w over
+// the resources with r > 0 only; the score is int64(math.Round(float64(s) / float64(ws))), 0 when ws == 0.  With
+// s ≤ 100·ws and ws ≤ 2·10⁶ that is (2s + ws) / (2ws) truncating: s/ws is a multiple of 1/ws, so a quotient that is not
+// an exact half lies at least 1/(2ws) ≥ 2.5·10⁻⁷ from one, while the f64 quotient of two exact integers is off by at
+// most 100.5 · 2⁻⁵³ ≈ 1.1·10⁻¹⁴; an exact half is exact in f64 and rounds away from zero, as (2s + ws) / (2ws) does.
 template <int MOST = -1>
 __device__ __forceinline__ bool eval_node(const Row& n, const DevPod& p, const EvalParams& P, int64_t& total,
                                           uint32_t* reject = nullptr, int64_t* fit_out = nullptr,
@@ -271,18 +294,31 @@ __device__ __forceinline__ bool eval_node(const Row& n, const DevPod& p, const E
   int64_t t = 0, fs = 0, ls = 0;
   if (P.fit_score || fit_out) {
     int64_t s = 0, ws = 0;
-    const bool most = MOST < 0 ? P.fit_most != 0 : MOST != 0;
-    if (P.fit_w_cpu && n.alloc_cpu != 0) {
-      const int64_t rc = n.nz_cpu + p.nz_cpu;
-      s += (most ? most_requested64(rc, n.alloc_cpu) : least_requested(rc, n.alloc_cpu)) * P.fit_w_cpu;
-      ws += P.fit_w_cpu;
+    const bool rtcr = MOST < 0 ? P.fit_rtcr != 0 : MOST == 2;
+    const bool most = MOST < 0 ? P.fit_most != 0 : MOST == 1;
+    if (rtcr) {
+      if (P.fit_w_cpu && n.alloc_cpu != 0) {
+        const int64_t r = fit_lut_at(P.fit_lut, (int32_t)most_requested64(n.nz_cpu + p.nz_cpu, n.alloc_cpu));
+        if (r > 0) s += r * P.fit_w_cpu, ws += P.fit_w_cpu;
+      }
+      if (P.fit_w_mem && n.alloc_mem != 0) {
+        const int64_t r = fit_lut_at(P.fit_lut, (int32_t)most_requested64(n.nz_mem + p.nz_mem, n.alloc_mem));
+        if (r > 0) s += r * P.fit_w_mem, ws += P.fit_w_mem;
+      }
+      fs = ws ? div_small(2 * s + ws, 2 * ws) : 0;
+    } else {
+      if (P.fit_w_cpu && n.alloc_cpu != 0) {
+        const int64_t rc = n.nz_cpu + p.nz_cpu;
+        s += (most ? most_requested64(rc, n.alloc_cpu) : least_requested(rc, n.alloc_cpu)) * P.fit_w_cpu;
+        ws += P.fit_w_cpu;
+      }
+      if (P.fit_w_mem && n.alloc_mem != 0) {
+        const int64_t rm = n.nz_mem + p.nz_mem;
+        s += (most ? most_requested64(rm, n.alloc_mem) : least_requested(rm, n.alloc_mem)) * P.fit_w_mem;
+        ws += P.fit_w_mem;
+      }
+      fs = ws ? div_small(s, ws) : 0;
     }
-    if (P.fit_w_mem && n.alloc_mem != 0) {
-      const int64_t rm = n.nz_mem + p.nz_mem;
-      s += (most ? most_requested64(rm, n.alloc_mem) : least_requested(rm, n.alloc_mem)) * P.fit_w_mem;
-      ws += P.fit_w_mem;
-    }
-    fs = ws ? div_small(s, ws) : 0;
     if (P.fit_score) t += fs * P.weight_fit;
   }
   if (P.la_score || la_out) {
@@ -521,6 +557,23 @@ __device__ __forceinline__ int32_t div_est(int32_t s, int32_t w, float inv_w) {
   return q;
 }
 
+// RequestedToCapacityRatio on the fast paths (PF_FIT_RTCR): the node's Fit score from the two utilization quotients
+// uc, um (mrs_*: in [0, 100] inside the domain; clamped for the lookup whatever they are) and the shape table `lut`
+// (LDS in the round kernels, device memory in the debug hooks).  A resource takes part when its weight is non-zero
+// (inside the domain its allocatable is > 0) and its shape value r is > 0, so Σ weights is per lane one of
+// {0, w_cpu, w_mem, w_cpu + w_mem}, with the reciprocal P.inv_fit_ws[mask].  round(s / ws) = (2s + ws) / (2ws)
+// truncating (eval_node's comment), by div_est with half the reciprocal: 2ws ≤ 4·10⁶ < 2²⁴ and q ≤ 101 keep its
+// 24-bit multiplies exact, 2s + ws ≤ 201 · 2·10⁶ < 2³¹, and the f32 estimate of a value ≤ 100.5 is within ±1.
+__device__ __forceinline__ int32_t fit_rtcr_score(const uint8_t* lut, int32_t uc, int32_t um, const EvalParams& P) {
+  const int32_t rc = fit_lut_at(lut, uc), rm = fit_lut_at(lut, um);
+  const int32_t wc = rc > 0 ? (int32_t)P.fit_w_cpu : 0, wm = rm > 0 ? (int32_t)P.fit_w_mem : 0;
+  const int32_t ws = wc + wm;
+  const float inv = wc ? (wm ? P.inv_fit_ws[3] : P.inv_fit_ws[1]) : (wm ? P.inv_fit_ws[2] : 0.0f);
+  const int32_t s = (int32_t)(__umul24((uint32_t)rc, (uint32_t)wc) + __umul24((uint32_t)rm, (uint32_t)wm));
+  const int32_t f = div_est(2 * s + ws, 2 * ws, 0.5f * inv);
+  return ws ? f : 0;
+}
+
 // Value selects the optimiser cannot turn into a select of field ADDRESSES: that rewrite (select of two loads
 // → load of a selected address) would keep a whole EvalRow array in scratch memory instead of registers.
 __device__ __forceinline__ int64_t pick(bool c, int64_t a, int64_t b) {
@@ -539,9 +592,10 @@ __device__ __forceinline__ double pick(bool c, double a, double b) {
 // Branch-free fused Filter + Score on hoisted terms, specialised on the profile PF.  Returns feasibility;
 // sets `rare` when the row lies outside the fast path's exact domain (F_RARE) — the caller then re-evaluates
 // with eval_node.
+// `lut`: the RequestedToCapacityRatio shape table, read under PF_FIT_RTCR only.
 template <int PF>
 __device__ __forceinline__ bool eval_fast(const EvalRow& n, const DevPod& p, const EvalParams& P, uint32_t& total,
-                                          bool& rare) {
+                                          bool& rare, const uint8_t* lut = nullptr) {
   const uint32_t pf = p.flags;
   bool ok = (n.flags & F_VALID) != 0;
   if constexpr ((PF & PF_FIT_FILTER) != 0) {
@@ -554,7 +608,12 @@ __device__ __forceinline__ bool eval_fast(const EvalRow& n, const DevPod& p, con
   }
   uint32_t t = 0;
   if constexpr ((PF & (PF_FIT_SCORE | PF_LA_SCORE)) != 0) rare |= (n.flags & F_RARE) != 0;
-  if constexpr ((PF & PF_FIT_SCORE) != 0) {
+  if constexpr ((PF & PF_FIT_RTCR) != 0) {
+    // a row inside the domain has allocatable > 0 for every weighted resource; any other is rare and re-evaluated
+    const int32_t uc = mrs_cpu((int32_t)n.fnz_cpu - p.nz_cpu32, (int32_t)n.alloc_cpu, n.inv_cpu);
+    const int32_t um = mrs_mem(n.fnz_mem - p.nz_mem_d, n.alloc_mem, n.inv_mem);
+    t += __umul24((uint32_t)fit_rtcr_score(lut, uc, um, P), (uint32_t)P.weight_fit);
+  } else if constexpr ((PF & PF_FIT_SCORE) != 0) {
     int32_t qc, qm;
     if constexpr ((PF & PF_FIT_MOST) != 0) {
       qc = mrs_cpu((int32_t)n.fnz_cpu - p.nz_cpu32, (int32_t)n.alloc_cpu, n.inv_cpu);
@@ -714,8 +773,10 @@ __device__ __forceinline__ HotRow load_hot(const DevTable& T, int64_t i, const E
 // eval_hot<PF>: eval_fast on a HotRow (caller guarantees !(flags & F_RARE)).  The pod's request/estimate
 // quantities come pre-narrowed in DevPod: req_cpu32 = min(req_cpu, 2^30 + 1) (any larger request fails the
 // 32-bit compare exactly as the int64 one does, since |free_cpu| ≤ 2^30), req_mem_d = min(req_mem, 2^53).
+// `lut`: the RequestedToCapacityRatio shape table (the block's LDS copy in eval_round), read under PF_FIT_RTCR only.
 template <int PF>
-__device__ __forceinline__ bool eval_hot(const HotRow& n, const DevPod& p, const EvalParams& P, uint32_t& total) {
+__device__ __forceinline__ bool eval_hot(const HotRow& n, const DevPod& p, const EvalParams& P, uint32_t& total,
+                                         const uint8_t* lut = nullptr) {
   const uint32_t pf = p.flags;
   bool ok = (n.flags & F_VALID) != 0;
   if constexpr ((PF & PF_FIT_FILTER) != 0) {
@@ -727,7 +788,12 @@ __device__ __forceinline__ bool eval_hot(const HotRow& n, const DevPod& p, const
     ok = ok & (((pf & P_DAEMONSET) != 0) | ((n.flags & passbit) != 0));
   }
   uint32_t t = 0;
-  if constexpr ((PF & PF_FIT_SCORE) != 0) {
+  if constexpr ((PF & PF_FIT_RTCR) != 0) {
+    // Σ weights is NOT the profile constant here: a resource whose shape value is 0 leaves it (fit_rtcr_score)
+    const int32_t uc = mrs_cpu(n.fnz_cpu - p.nz_cpu32, n.alloc_cpu, n.inv_cpu);
+    const int32_t um = mrs_mem(n.fnz_mem - p.nz_mem_d, n.alloc_mem, n.inv_mem);
+    t += __umul24((uint32_t)fit_rtcr_score(lut, uc, um, P), (uint32_t)P.weight_fit);
+  } else if constexpr ((PF & PF_FIT_SCORE) != 0) {
     int32_t qc, qm;
     if constexpr ((PF & PF_FIT_MOST) != 0) {
       qc = mrs_cpu(n.fnz_cpu - p.nz_cpu32, n.alloc_cpu, n.inv_cpu);

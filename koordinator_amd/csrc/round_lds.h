@@ -78,10 +78,11 @@ struct LdsLayout {
 };
 
 // ---- resolve_round<PF, QUOTA> --------------------------------------------------------------------------------------
+// `shape`: the profile scores RequestedToCapacityRatio (PF_FIT_RTCR) and the kernel keeps the shape table in LDS
 struct ResolveLds : LdsLayout {
-  uint32_t cand, pods, par, hash, prevn, bitmap;
+  uint32_t cand, pods, par, hash, prevn, bitmap, lut;
 };
-__host__ __device__ constexpr ResolveLds resolve_lds(int nb, int bitmap_words) {
+__host__ __device__ constexpr ResolveLds resolve_lds(int nb, int bitmap_words, bool shape = false) {
   LdsCarver c;
   ResolveLds L{};
   L.cand = c.take<uint64_t, 16>(nb * kCandStride);  // [nb][kCandStride] the pods' records (LDS-DMA)
@@ -90,6 +91,9 @@ __host__ __device__ constexpr ResolveLds resolve_lds(int nb, int bitmap_words) {
   L.hash = c.take<uint32_t, 16>(kModHash);          // node → slot (uint4 clears)
   L.prevn = c.take<uint32_t>(kMaxMod);              // earlier rounds' nodes
   L.bitmap = c.take<uint32_t, 16>(bitmap_words);    // modified rows (uint4 clears)
+  // lut[0..100] as uint8_t, zero-padded (only with `shape`).  Bytes, not words: 101 bytes span 26 dwords, fewer than
+  // the 64 banks, so two lanes on one bank read the same dword and a per-lane byte lookup cannot conflict
+  L.lut = c.take<uint8_t, 16>(shape ? kFitLutBytes : 0);
   L.end = c.bytes();
   return L;
 }
@@ -202,10 +206,11 @@ __host__ __device__ constexpr XrLds xr_lds(int xf, int nq, bool aux, int bitmap_
 // parks tile lists instead: [ew][ppw·kR] uint64, ppw lists of kR keys per wave (the stride the kernel indexes with).
 constexpr uint32_t kEvalStageCap = 64 * 1024;
 struct EvalLds : LdsLayout {
-  uint32_t lists, vals, sel;
+  uint32_t lists, vals, sel, lut;
   bool staged;  // the values are staged and selected per (pod, tile group); else tile lists (combined if `combine`)
 };
-__host__ __device__ constexpr EvalLds eval_lds(int ew, int tile_nodes, int rg, int ppw, bool combine) {
+__host__ __device__ constexpr EvalLds eval_lds(int ew, int tile_nodes, int rg, int ppw, bool combine,
+                                               bool shape = false) {
   LdsCarver c;
   EvalLds L{};
   const uint32_t vals = (uint32_t)ew * (uint32_t)ppw * (uint32_t)tile_nodes;
@@ -216,6 +221,9 @@ __host__ __device__ constexpr EvalLds eval_lds(int ew, int tile_nodes, int rg, i
   } else {
     L.lists = c.take<uint64_t, 16>(ew * ppw * kR);  // [ew][ppw][kR]
   }
+  // the RequestedToCapacityRatio shape table (only with `shape`, PF_FIT_RTCR; as resolve_lds's): after the staging
+  // decision, which therefore is the same with and without it
+  L.lut = c.take<uint8_t, 16>(shape ? kFitLutBytes : 0);
   L.end = c.bytes();
   return L;
 }
@@ -237,6 +245,12 @@ static_assert(eval_lds(8, 128, 8, 15, true).staged && eval_lds(8, 128, 8, 15, tr
                   !eval_lds(8, 128, 8, 16, true).staged && eval_lds(8, 128, 8, kMaxB, true).bytes() <= kEvalStageCap &&
                   eval_lds(8, 128, 8, kMaxB, false).bytes() <= kEvalStageCap,
               "eval_round: staged up to 15 pods per wave, tile lists beyond, 64 KiB at most either way");
+static_assert(resolve_lds(kMaxB, kMaxBitmapWords, true).bytes() <= kMaxLds &&
+                  2 * eval_lds(8, 128, 8, 8, true, true).bytes() <= kMaxLds &&
+                  eval_lds(8, 128, 8, 15, true, true).bytes() <= kEvalStageCap &&
+                  eval_lds(8, 128, 8, kMaxB, true, true).bytes() <= kEvalStageCap &&
+                  eval_lds(8, 128, 8, kMaxB, false, true).bytes() <= kEvalStageCap,
+              "the same bounds with the RequestedToCapacityRatio shape table");
 static_assert(numa_lds(kMaxB, kMaxBitmapWords).bytes() <= kMaxLds, "resolve_round_numa at kMaxB pods, kMaxNodes nodes");
 static_assert(xr_lds(XF_NUMA | XF_DS | XF_DEF, KG_MAX_QUOTAS, true, kMaxBitmapWords).bytes() <= kMaxLds,
               "xr_resolve with every section at kMaxNodes nodes");

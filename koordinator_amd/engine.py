@@ -74,7 +74,7 @@ class Engine:
 
     def __init__(self, config: np.ndarray, capacity: int, rank: int = 0, n_ranks: int = 1,
                  nccl_id: bytes | None = None, loopback: Loopback | None = None,
-                 exchange: HostExchange | None = None):
+                 exchange: HostExchange | None = None, fit_shape=None):
         self.lib = abi.load_library()
         self._cfg = np.array(config, dtype=abi.CONFIG_DTYPE).reshape(1)
         h = ctypes.c_void_p()
@@ -94,6 +94,12 @@ class Engine:
                                                       ctypes.byref(h)))
         self.h = h
         self.capacity = capacity
+        if fit_shape is not None:  # NodeResourcesFit RequestedToCapacityRatio: kg_config cannot carry the shape
+            try:
+                self.set_fit_shape(fit_shape)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifecycle -------------------------------------------------------------------------------------
     def close(self):
@@ -752,6 +758,37 @@ class Engine:
         check(self.lib, self.lib.kg_debug_fast_lrs(self.h, ptr(requested), ptr(capacity), ptr(oc), ptr(om),
                                                    len(requested)))
         return oc, om
+
+    # -- NodeResourcesFit RequestedToCapacityRatio -----------------------------------------------------------------
+    def set_fit_shape(self, points):
+        """Score NodeResourcesFit by RequestedToCapacityRatio with this shape: (utilization, score) pairs or an array of
+        abi.SHAPE_POINT_DTYPE.  None or an empty shape returns to the configured strategy.  The engine validates."""
+        if points is None:
+            points = []
+        if isinstance(points, np.ndarray) and points.dtype == abi.SHAPE_POINT_DTYPE:
+            arr = np.ascontiguousarray(points)
+        else:
+            arr = np.array([(int(u), int(s)) for u, s in points], dtype=abi.SHAPE_POINT_DTYPE)
+        check(self.lib, self.lib.kg_fit_shape_set(self.h, ptr(arr) if len(arr) else None, len(arr)))
+
+    def fit_shape(self):
+        """(the table raw(0..100) the engine scores with, whether RequestedToCapacityRatio is active)."""
+        lut = np.zeros(101, dtype=np.int64)
+        active = ctypes.c_int64(0)
+        check(self.lib, self.lib.kg_fit_shape_get(self.h, ptr(lut), ctypes.byref(active)))
+        return lut, bool(active.value)
+
+    def debug_fit_shape(self, requested, capacity):
+        """(reference-shaped, cpu-routine, memory-routine) per-resource shape score; a fast routine gives -1 outside its
+        domain."""
+        requested = np.ascontiguousarray(requested, dtype=np.int64)
+        capacity = np.ascontiguousarray(capacity, dtype=np.int64)
+        ref = np.zeros(len(requested), dtype=np.int64)
+        oc = np.zeros(len(requested), dtype=np.int64)
+        om = np.zeros(len(requested), dtype=np.int64)
+        check(self.lib, self.lib.kg_debug_fit_shape(self.h, ptr(requested), ptr(capacity), ptr(ref), ptr(oc), ptr(om),
+                                                    len(requested)))
+        return ref, oc, om
 
     def debug_fast_mrs(self, requested, capacity):
         """(reference-shaped, cpu-routine, memory-routine) mostRequestedScore; a fast routine gives -1 outside its domain."""

@@ -134,9 +134,32 @@ class LoadAwareSchedulingArgs:
 
 @dataclass
 class NodeResourcesFitArgs:
-    """Upstream NodeResourcesFitArgs.ScoringStrategy: Type (LeastAllocated / MostAllocated) and Resources weights."""
+    """Upstream NodeResourcesFitArgs.ScoringStrategy: Type (LeastAllocated / MostAllocated / RequestedToCapacityRatio),
+    Resources weights and, for RequestedToCapacityRatio, RequestedToCapacityRatio.Shape as (utilization, score) pairs.
+    kg_config has no room for a shape: build_config leaves the strategy word 0 for it, and the shape goes to the engine
+    right after create — Scheduler(config, capacity, fit=args) / Engine(..., fit_shape=args.shape) do that."""
     scoring_resources: dict = field(default_factory=lambda: {"cpu": 1, "memory": 1})
     scoring_strategy: str = "LeastAllocated"
+    shape: list | None = None
+
+
+REQUESTED_TO_CAPACITY_RATIO = "RequestedToCapacityRatio"
+
+
+def validate_fit_shape(points) -> np.ndarray:
+    """The shape as an array of kg_shape_point, after kg_fit_shape_set's checks: 1 to 101 points, utilization strictly
+    increasing within [0, 100], score within [0, 10].  ValueError otherwise."""
+    pts = [(int(u), int(s)) for u, s in points]
+    if not 1 <= len(pts) <= abi.FIT_SHAPE_MAX_POINTS:
+        raise ValueError(f"RequestedToCapacityRatio shape: {len(pts)} points (1 to {abi.FIT_SHAPE_MAX_POINTS})")
+    for i, (u, sc) in enumerate(pts):
+        if not 0 <= u <= 100:
+            raise ValueError(f"RequestedToCapacityRatio shape point {i}: utilization {u} outside [0, 100]")
+        if i and u <= pts[i - 1][0]:
+            raise ValueError(f"RequestedToCapacityRatio shape point {i}: utilization must be strictly increasing")
+        if not 0 <= sc <= 10:
+            raise ValueError(f"RequestedToCapacityRatio shape point {i}: score {sc} outside [0, 10]")
+    return np.array(pts, dtype=abi.SHAPE_POINT_DTYPE)
 
 
 @dataclass
@@ -196,11 +219,16 @@ def build_config(la: LoadAwareSchedulingArgs | None = None, fit: NodeResourcesFi
     r["la_agg_score_type"] = abi.AGG_TYPES[agg.get("score_type", "")]
     r["la_agg_score_duration_ns"] = int(agg.get("score_duration_s", 0) * 10**9)
     r["fit_resource_weights"] = _slots(fit.scoring_resources)
-    if fit.scoring_strategy not in abi.STRATEGY:
-        # RequestedToCapacityRatio (its shape function) is not accelerated: such a profile keeps the Go path
+    if fit.scoring_strategy == REQUESTED_TO_CAPACITY_RATIO and fit.shape is not None:
+        # the shape travels by kg_fit_shape_set after create (Scheduler(..., fit=fit)); the config word stays 0
+        validate_fit_shape(fit.shape)
+        r["fit_scoring_strategy"] = 0
+    elif fit.scoring_strategy not in abi.STRATEGY:
+        # RequestedToCapacityRatio without its shape, or an unknown type
         raise ValueError(f"NodeResourcesFitArgs.ScoringStrategy.Type {fit.scoring_strategy!r}: the engine scores "
-                         f"{' / '.join(abi.STRATEGY)}")
-    r["fit_scoring_strategy"] = abi.STRATEGY[fit.scoring_strategy]
+                         f"{' / '.join(abi.STRATEGY)}, and {REQUESTED_TO_CAPACITY_RATIO} given its shape")
+    else:
+        r["fit_scoring_strategy"] = abi.STRATEGY[fit.scoring_strategy]
     r["fit_filter"] = int(NODE_RESOURCES_FIT in profile.filter)
     r["la_filter"] = int(LOAD_AWARE in profile.filter)
     r["fit_score"] = int(NODE_RESOURCES_FIT in profile.score)
@@ -454,8 +482,12 @@ class ScheduleResult:
 class Scheduler:
     """SchedulePod / RunFilterPlugins / RunScorePlugins over the GPU engine."""
 
-    def __init__(self, config: np.ndarray, capacity: int, **kw):
+    def __init__(self, config: np.ndarray, capacity: int, fit: NodeResourcesFitArgs | None = None, **kw):
+        """fit: the NodeResourcesFitArgs the config was built from; its RequestedToCapacityRatio shape, which kg_config
+        cannot carry, is applied to the engine right after create."""
         self.config = config
+        if fit is not None and fit.scoring_strategy == REQUESTED_TO_CAPACITY_RATIO:
+            kw["fit_shape"] = validate_fit_shape(fit.shape if fit.shape is not None else [])
         self.engine = Engine(config, capacity, **kw)
         self._nominated = {}  # the nominator mirror: uid -> (pod record, PodPriority, node), in insertion order
 
