@@ -853,6 +853,14 @@ int kg_fit_shape_get(kg_engine* e, int64_t* out_lut101, int64_t* out_active);
 int kg_debug_fit_shape(kg_engine* e, const int64_t* requested, const int64_t* capacity, int64_t* out_ref,
                        int64_t* out_cpu, int64_t* out_mem, int64_t n);
 
+/* (within ABI 18) Debug: NodeResourcesBalancedAllocation's score of n (Allocatable, Requested, pod request) triples two
+ * ways.  alloc / requested / pod hold 2n values each: the n cpu values, then the n memory values; `resources` is
+ * kg_config.balanced_resources (bit 0 cpu, bit 1 memory).  out_ref = the reference-shaped routine of the exact paths
+ * (any input); out_hot = the round engine's form on its hoisted terms, with the pod's request clamped as the wide pass
+ * carries it (-1 where the row lies outside that form's exact domain: the engine sends such rows to the exact path). */
+int kg_debug_balanced(kg_engine* e, const int64_t* alloc, const int64_t* requested, const int64_t* pod,
+                      int64_t resources, int64_t* out_ref, int64_t* out_hot, int64_t n);
+
 /* Debug: the device topology-manager policy merge — Policy.Merge + canAdmitPodResult over ≤ 2 filtered provider lists
  * (frameworkext/topologymanager/policy.go:127-185 mergeFilteredHints, policy_best_effort.go:43-48,
  * policy_restricted.go:41-46, policy_single_numa_node.go:38-77) — exactly the code NodeNUMAResource Filter runs, on n
@@ -880,7 +888,8 @@ int kg_debug_eval_paths(kg_engine* e, int64_t* mismatches);
  *   out_lists   uint64[nb][lists per pod][words per list], lists_cap_words words available
  *   out_records uint64[nb][kC + 1]: the record's keys (descending, 0-padded), then its bound ub
  * A key is score << 32 | ~node index (32 bits); 0 = no candidate.
- * KG_E_UNSUPPORTED: NUMA, DeviceShare, Reservation / exact-pass profiles, several ranks.  KG_E_INVALID: a range outside
+ * KG_E_UNSUPPORTED: NUMA, DeviceShare, Reservation / exact-pass profiles (but for NodeResourcesBalancedAllocation alone
+ * beside Fit / LoadAware, which the round engine runs: DESIGN.md 3.26), several ranks.  KG_E_INVALID: a range outside
  * the staged queue or longer than a round, a lists buffer too small.
  *
  * kg_debug_merge merges caller-given lists: lists = uint64[n_pods][n_lists][list_len], out_records as above.

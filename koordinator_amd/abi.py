@@ -260,6 +260,7 @@ EXPORTED_SYMBOLS = (
     "kg_nodes_read_state", "kg_bench_kernel", "kg_debug_least_requested", "kg_last_error", "kg_abi_version",
     "kg_abi_struct_size", "kg_nccl_unique_id", "kg_debug_rccl_selftest", "kg_debug_eval_paths", "kg_debug_stamps",
     "kg_debug_fast_lrs", "kg_debug_fast_mrs", "kg_fit_shape_set", "kg_fit_shape_get", "kg_debug_fit_shape",
+    "kg_debug_balanced",
     "kg_nodes_numa_upsert", "kg_nodes_read_numa", "kg_results_fetch_cpusets", "kg_pods_evaluate_numa",
     "kg_nodes_device_upsert", "kg_nodes_read_device", "kg_results_fetch_devices", "kg_pods_evaluate_device",
     "kg_results_fetch_devices_x", "kg_nodes_read_device_x",
@@ -347,6 +348,7 @@ def load_library(path: str | None = None):
         "kg_fit_shape_set": (i, [vp, vp, i64]),
         "kg_fit_shape_get": (i, [vp, vp, vp]),
         "kg_debug_fit_shape": (i, [vp, vp, vp, vp, vp, vp, i64]),
+        "kg_debug_balanced": (i, [vp, vp, vp, vp, i64, vp, vp, i64]),
         "kg_nodes_numa_upsert": (i, [vp, vp, vp, i64]),
         "kg_nodes_read_numa": (i, [vp, vp, vp, vp]),
         "kg_results_fetch_cpusets": (i, [vp, i64, i64, vp]),

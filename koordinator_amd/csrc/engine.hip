@@ -336,7 +336,7 @@ __device__ __forceinline__ void group_select_write(const uint32_t (&x)[NV], uint
 // A tile holding a row outside eval_hot's exact domain: the reference-shaped int64 path for every pod (rare).
 // The row index is laundered inside the loop so the compiler cannot hoist the 19 column addresses out of it
 // (they would stay live across the wide loop and halve its occupancy).
-template <int NPT, int MOST, class Sink>
+template <int NPT, int MOST, int BAL, class Sink>
 __device__ __forceinline__ void eval_tile_exact(const DevTable& T, const DevPod* __restrict__ pods, int64_t first,
                                              int p0, int p1, int tile, int64_t node_base, int64_t n_local,
                                              const EvalParams& P, const Sink& sink,
@@ -353,7 +353,7 @@ __device__ __forceinline__ void eval_tile_exact(const DevTable& T, const DevPod*
       int64_t local = (int64_t)tile * (kWave * NPT) + j * kWave + lane;
       asm volatile("" : "+v"(local));
       int64_t t = 0;
-      v[j] = (local < n_local && eval_node<MOST>(load_row(T, node_base + local), p, P, t)) ? (uint32_t)t + 1u : 0u;
+      v[j] = (local < n_local && eval_node<MOST, BAL>(load_row(T, node_base + local), p, P, t)) ? (uint32_t)t + 1u : 0u;
       if (P.fit_filter && (p.flags & P_AUX) && v[j] && !aux_fits(T, node_base + local, paux + (size_t)(first + pi) * kAux))
         v[j] = 0;
     }
@@ -396,7 +396,7 @@ __device__ __forceinline__ void eval_tile(const DevTable& T, const DevPod* __res
   KG_STAMP(0, 1);
   // a row outside eval_hot's exact domain anywhere in the tile: the whole tile takes the exact path
   if (__ballot(rare)) {
-    eval_tile_exact<NPT, fit_strategy_of(PF)>(T, pods, first, p0, p1, tile, node_base, n_local, P, sink, paux);
+    eval_tile_exact<NPT, fit_strategy_of(PF), (PF & PF_BAL) ? 1 : 0>(T, pods, first, p0, p1, tile, node_base, n_local, P, sink, paux);
     return;
   }
   for (int pi = p0; pi < p1; ++pi) {
@@ -1059,7 +1059,7 @@ __device__ __forceinline__ uint64_t mod_key(const EvalRow& er, uint32_t node, co
     EvalParams Pr;
     __builtin_memcpy(&Pr, q, sizeof(Pr));
     int64_t t64 = 0;
-    ok = eval_node<fit_strategy_of(PF)>(row_of(er), p, Pr, t64);
+    ok = eval_node<fit_strategy_of(PF), (PF & PF_BAL) ? 1 : 0>(row_of(er), p, Pr, t64);
     t = (uint32_t)t64;
   }
   return ok ? make_key(t, node) : 0;
@@ -1119,6 +1119,8 @@ __device__ __forceinline__ void assume_mod(EvalRow& e, const DevPod& p, const Ev
       out |= (e.la_free_cpu < kCpuFreeMin) | (e.la_pfree_cpu < kCpuFreeMin) | !(e.la_free_mem > (double)kMemFreeMin) |
              !(e.la_pfree_mem > (double)kMemFreeMin);
   }
+  // NodeResourcesBalancedAllocation scores the Requested free terms (balanced_hot's domain)
+  if constexpr ((PF & PF_BAL) != 0) out |= (e.free_cpu < kCpuFreeMin) | !(e.free_mem > kMemFreeMin);
   if (out) e.flags |= F_RARE;
 }
 
@@ -1225,7 +1227,7 @@ __device__ __forceinline__ void mod_row_settle(ModRow& R, const uint64_t* s_cand
   if (R.pend >= 0) {
     const int pj = R.pend >> 8, ppos = R.pend & 0xFF;
     if (ppos < kStaged) R.er = lds_row(s_cand + (size_t)pj * kCandStride + kRecRows + ppos * kEvalRowWords);
-    else R.er = make_eval_row(load_row(table_at(T0), R.node), P);
+    else R.er = make_eval_row<(PF & PF_BAL) ? 1 : 0>(load_row(table_at(T0), R.node), P);
     assume_mod<PF>(R.er, s_pods[pj], P);
     R.pend = -1;
   }
@@ -1316,7 +1318,7 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
     const uint32_t node = s_prevn[lane];
     if (mod_insert(s_hash, node, lane) == lane) {
       R0.node = node;
-      R0.er = make_eval_row(load_row(table_at(T0), node), P);
+      R0.er = make_eval_row<(PF & PF_BAL) ? 1 : 0>(load_row(table_at(T0), node), P);
       atomicOr(&bitmap[node >> 5], 1u << (node & 31));
     }
   }
@@ -1324,7 +1326,7 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
     const uint32_t node = s_prevn[kWave + lane];
     if (mod_insert(s_hash, node, kWave + lane) == kWave + lane) {
       R1.node = node;
-      R1.er = make_eval_row(load_row(table_at(T0), node), P);
+      R1.er = make_eval_row<(PF & PF_BAL) ? 1 : 0>(load_row(table_at(T0), node), P);
       atomicOr(&bitmap[node >> 5], 1u << (node & 31));
     }
   }
@@ -1376,7 +1378,8 @@ __global__ __launch_bounds__(kWave) void resolve_round(DevTable T0, const DevPod
       // raises the winner's key, so a modified row may beat e wherever it is listed, or unlisted — every pod re-scores
       // every modified row.  RequestedToCapacityRatio (PF_FIT_RTCR) is not monotone for any shape and
       // takes the same rule (§3.25)
-      constexpr bool kMost = (PF & (PF_FIT_MOST | PF_FIT_RTCR)) != 0;
+      // NodeResourcesBalancedAllocation (PF_BAL): a cpu-heavy pod on a memory-heavy node raises its key — the same (§3.26)
+      constexpr bool kMost = (PF & (PF_FIT_MOST | PF_FIT_RTCR | PF_BAL)) != 0;
       if (nM > 0 && (kMost || pos > 0)) {
         if (!QUOTA) p = s_pods[j];
         ++n_slow;
@@ -3077,7 +3080,7 @@ __device__ __forceinline__ bool eval_hot_rt(const DevTable& T, int64_t i, const 
   const int pf = (P.fit_filter ? PF_FIT_FILTER : 0) | (P.fit_score ? PF_FIT_SCORE : 0) |
                  (P.la_filter ? PF_LA_FILTER : 0) | (P.la_score ? PF_LA_SCORE : 0) |
                  (P.la_score && P.la_prod_score ? PF_LA_PROD : 0) | (P.fit_score && P.fit_most ? PF_FIT_MOST : 0) |
-                 (P.fit_score && P.fit_rtcr ? PF_FIT_RTCR : 0);
+                 (P.fit_score && P.fit_rtcr ? PF_FIT_RTCR : 0) | (P.bal ? PF_BAL : 0);
   switch (pf) {
 #define KG_CASE(X)                                   \
   case X: {                                          \
@@ -3092,6 +3095,8 @@ __device__ __forceinline__ bool eval_hot_rt(const DevTable& T, int64_t i, const 
     KG_CASE(58) KG_CASE(59) KG_CASE(62) KG_CASE(63)
     KG_CASE(66) KG_CASE(67) KG_CASE(70) KG_CASE(71) KG_CASE(74) KG_CASE(75) KG_CASE(78) KG_CASE(79)
     KG_CASE(90) KG_CASE(91) KG_CASE(94) KG_CASE(95)
+    KG_CASE(128) KG_CASE(129) KG_CASE(130) KG_CASE(131) KG_CASE(132) KG_CASE(133) KG_CASE(134) KG_CASE(135)
+    KG_CASE(136) KG_CASE(137) KG_CASE(138) KG_CASE(139) KG_CASE(140) KG_CASE(141) KG_CASE(142) KG_CASE(143)
 #undef KG_CASE
   }
   return false;
@@ -3101,7 +3106,8 @@ __device__ __forceinline__ bool eval_fast_rt(const EvalRow& n, const DevPod& p, 
                                              bool& rare) {
   const int pf = (P.fit_filter ? PF_FIT_FILTER : 0) | (P.fit_score ? PF_FIT_SCORE : 0) |
                  (P.la_filter ? PF_LA_FILTER : 0) | (P.la_score ? PF_LA_SCORE : 0) |
-                 (P.fit_score && P.fit_most ? PF_FIT_MOST : 0) | (P.fit_score && P.fit_rtcr ? PF_FIT_RTCR : 0);
+                 (P.fit_score && P.fit_most ? PF_FIT_MOST : 0) | (P.fit_score && P.fit_rtcr ? PF_FIT_RTCR : 0) |
+                 (P.bal ? PF_BAL : 0);
   switch (pf) {
 #define KG_CASE(X) \
   case X:          \
@@ -3110,6 +3116,8 @@ __device__ __forceinline__ bool eval_fast_rt(const EvalRow& n, const DevPod& p, 
     KG_CASE(8) KG_CASE(9) KG_CASE(10) KG_CASE(11) KG_CASE(12) KG_CASE(13) KG_CASE(14) KG_CASE(15)
     KG_CASE(34) KG_CASE(35) KG_CASE(38) KG_CASE(39) KG_CASE(42) KG_CASE(43) KG_CASE(46) KG_CASE(47)
     KG_CASE(66) KG_CASE(67) KG_CASE(70) KG_CASE(71) KG_CASE(74) KG_CASE(75) KG_CASE(78) KG_CASE(79)
+    KG_CASE(128) KG_CASE(129) KG_CASE(130) KG_CASE(131) KG_CASE(132) KG_CASE(133) KG_CASE(134) KG_CASE(135)
+    KG_CASE(136) KG_CASE(137) KG_CASE(138) KG_CASE(139) KG_CASE(140) KG_CASE(141) KG_CASE(142) KG_CASE(143)
 #undef KG_CASE
   }
   return false;
@@ -3126,7 +3134,7 @@ __global__ void debug_eval_paths(DevTable T, const DevPod* __restrict__ pods, in
   for (int64_t k = 0; k < n_pods; ++k) {
     int64_t t1 = 0;
     uint32_t t2 = 0;
-    const bool f1 = eval_node(r, pods[k], P, t1);
+    const bool f1 = eval_node<-1, 1>(r, pods[k], P, t1);  // (with the Balanced term where P.bal routes the profile)
     bool rare = false;
     const bool f2 = eval_fast_rt(er, pods[k], P, t2, rare);
     bad += !rare && ((f1 != f2) || (f1 && (uint32_t)t1 != t2));
@@ -3219,6 +3227,32 @@ __global__ void debug_fit_shape(const uint8_t* __restrict__ lut, const int64_t* 
   } else {
     out_mem[i] = -1;
   }
+}
+
+// kg_debug_balanced: NodeResourcesBalancedAllocation's score of n (Allocatable, Requested, pod request) triples — each
+// array holds the cpu values, then the memory values — two ways: balanced_score (reference-shaped, any input) and the
+// fast paths' balanced_hot on the hoisted terms with the pod's request clamped as DevPod carries it (−1 outside
+// balanced_hot's domain, as hot_from_cols / rare_bit decide it)
+__global__ void debug_balanced(const int64_t* alloc, const int64_t* req, const int64_t* pod, int32_t bal,
+                               int64_t* out_ref, int64_t* out_hot, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t ac = alloc[i], am = alloc[n + i], rc = req[i], rm = req[n + i], pc = pod[i], pm = pod[n + i];
+  DefParams F{};
+  F.bal_cpu = (bal & kBalCpu) != 0, F.bal_mem = (bal & kBalMem) != 0;
+  out_ref[i] = balanced_score(ac, am, rc, rm, pc, pm, F);
+  // free = Allocatable − Requested in wrapping arithmetic, as the column subtraction of the wide pass
+  const int64_t fc = (int64_t)((uint64_t)ac - (uint64_t)rc), fm = (int64_t)((uint64_t)am - (uint64_t)rm);
+  bool ok = true;
+  if (bal & kBalCpu) ok &= cpu_dom(ac, fc);
+  if (bal & kBalMem) ok &= mem_dom(am, fm);
+  if (!ok) {
+    out_hot[i] = -1;
+    return;
+  }
+  const int64_t pc32 = pc < kPodCpu32Max + 1 ? pc : kPodCpu32Max + 1, pmd = pm < (1ll << 53) ? pm : (1ll << 53);
+  out_hot[i] = balanced_hot((double)(int32_t)((int32_t)ac - (int32_t)fc), (double)(int32_t)ac, (double)(int32_t)pc32,
+                            (double)am - (double)fm, (double)am, (double)pmd, bal);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3493,6 +3527,10 @@ struct kg_engine {
   // the per-pod exact pass (rsv_eval / rsv_select / rsv_apply) runs the profile: Reservation, or NodeNUMAResource
   // together with DeviceShare (the reference's shipped profile, config/manager/scheduler-config.yaml:66-117)
   bool exact_on = false;
+  // NodeResourcesBalancedAllocation next to Fit / LoadAware only, on one rank: batch calls of more than kExactSmall pods
+  // take the round engine (P.bal, PF_BAL) instead of the batched exact rounds; def_on / exact_on stay set — the exact
+  // pass's tables exist and the per-pod entry points answer as before
+  bool bal_rounds = false;
   DevBuf<uint32_t> numa_aff;  // exact pass: the NUMA affinity Filter stored per node for the pass's pod
   RsvParams RP{};
   DevBuf<RsvNode> rsv_d;
@@ -4390,7 +4428,9 @@ RoundGeom geometry(const kg_engine* e) {
   // resolver re-scores every row modified since the snapshot for every pod, and a torn read can only be of such a row
   // (DESIGN.md §3.24); depth · B ≤ kMaxMod above bounds its slots as it does the monotone profiles'
   // RequestedToCapacityRatio (kg_fit_shape_set) takes the same resolver rule and keeps the depth for the same reason
-  const bool most_rounds = e->P.fit_score && (e->P.fit_most || e->P.fit_rtcr) && !e->numa_on && !e->ds_on && !e->rsv_on;
+  // NodeResourcesBalancedAllocation on the round engine (bal_rounds) likewise (§3.26)
+  const bool most_rounds = ((e->P.fit_score && (e->P.fit_most || e->P.fit_rtcr)) || e->bal_rounds) && !e->numa_on &&
+                           !e->ds_on && !e->rsv_on;
   g.depth = (e->P.monotone || numa_rounds || most_rounds) ? d : 1;
   if (e->numa_on) g.ppw = std::min(g.ppw, kNumaPpw);  // eval_round_numa parks ≤ kNumaPpw pods' values in LDS
   if (e->ds_on) g.ppw = std::min(g.ppw, kDsPpw);      // the DeviceShare passes keep ≤ kDsPpw pods in registers
@@ -4411,12 +4451,16 @@ dim3 eval_grid(const RoundGeom& g, int nb) {
 int profile_bits(const EvalParams& P) {
   return (P.fit_filter ? PF_FIT_FILTER : 0) | (P.fit_score ? PF_FIT_SCORE : 0) | (P.la_filter ? PF_LA_FILTER : 0) |
          (P.la_score ? PF_LA_SCORE : 0) | (P.la_score && P.la_prod_score ? PF_LA_PROD : 0) |
-         (P.fit_score && P.fit_most ? PF_FIT_MOST : 0) | (P.fit_score && P.fit_rtcr ? PF_FIT_RTCR : 0);
+         (P.fit_score && P.fit_most ? PF_FIT_MOST : 0) | (P.fit_score && P.fit_rtcr ? PF_FIT_RTCR : 0) |
+         (P.bal ? PF_BAL : 0);
 }
 
 // PF_FIT_MOST (32) is legal only with PF_FIT_SCORE (2): the 8 Fit-scoring profiles of 0..15 and the 4 of 24..31, + 32.
 // PF_FIT_RTCR (64) likewise, and never with PF_FIT_MOST: the same 12, + 64.  Its cases come last, so that the kernels
 // they instantiate are emitted after every earlier one.
+// PF_BAL (128) is legal with each LeastAllocated profile 0..15 (Fit Score or not), never with PF_FIT_MOST / PF_FIT_RTCR,
+// and the PF_LA_PROD profiles 24..31 keep the exact pass (a routing decision: engine_create leaves P.bal 0 for them), so
+// 16 cases, again listed last.
 #ifdef KG_DEV_PF  // iteration builds only (make dev): one profile (any legal one, the + 32 ones included) instantiated;
                   // engine_create refuses every other one
 #define KG_PF_SWITCH(pf, CALL) \
@@ -4449,6 +4493,10 @@ int profile_bits(const EvalParams& P) {
     case 66: CALL(66); break; case 67: CALL(67); break; case 70: CALL(70); break; case 71: CALL(71); break;   \
     case 74: CALL(74); break; case 75: CALL(75); break; case 78: CALL(78); break; case 79: CALL(79); break;   \
     case 90: CALL(90); break; case 91: CALL(91); break; case 94: CALL(94); break; case 95: CALL(95); break;   \
+    case 128: CALL(128); break; case 129: CALL(129); break; case 130: CALL(130); break; case 131: CALL(131); break; \
+    case 132: CALL(132); break; case 133: CALL(133); break; case 134: CALL(134); break; case 135: CALL(135); break; \
+    case 136: CALL(136); break; case 137: CALL(137); break; case 138: CALL(138); break; case 139: CALL(139); break; \
+    case 140: CALL(140); break; case 141: CALL(141); break; case 142: CALL(142); break; case 143: CALL(143); break; \
   }
 #endif
 
@@ -5431,6 +5479,13 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
       return bail(fail(KG_E_UNSUPPORTED, "NodeResourcesFit MostAllocated together with %s keeps the Go path (its resolver "
                                          "is exact for the Fit + LoadAware round engine on one rank only)", with));
   }
+  // NodeResourcesBalancedAllocation with nothing but NodeResourcesFit (LeastAllocated) / LoadAwareScheduling around it,
+  // on an engine created with one rank: the round engine scores it (PF_BAL).  ScoreAccordingProdUsage profiles keep the
+  // exact pass — a routing decision that halves the new instantiations, not a refusal
+  e->bal_rounds = c.balanced_score && !(c.taint_filter || c.taint_score || c.affinity_filter || c.affinity_score ||
+                                        c.image_score || e->grp_on || e->numa_on || e->ds_on || e->rsv_on) &&
+                  c.fit_scoring_strategy == KG_STRATEGY_LEAST_ALLOCATED &&
+                  !(c.la_score && c.la_score_according_prod_usage) && n_ranks == 1;
   if (n_ranks > 1) {
     const bool heavy_exact = e->exact_on && !e->grp_on && (e->numa_on || e->ds_on);
     const bool shard = c.multi_rank_mode == KG_MULTI_RANK_SHARD ||
@@ -5526,6 +5581,11 @@ static int engine_create(const kg_config* cfg, int64_t capacity_nodes, int rank,
   // NodeResourcesFit MostAllocated: an assume raises the winner's Fit score
   e->P.fit_most = (int32_t)(c.fit_scoring_strategy == KG_STRATEGY_MOST_ALLOCATED);
   if (e->P.fit_most && e->P.fit_score) e->P.monotone = 0;
+  // NodeResourcesBalancedAllocation on the round engine: an assume can raise the winner's key
+  e->P.bal = e->bal_rounds ? (kBalOn | (c.balanced_resources & 1 ? kBalCpu : 0) | (c.balanced_resources & 2 ? kBalMem : 0) |
+                              (int32_t)c.weight_balanced)
+                           : 0;
+  if (e->bal_rounds) e->P.monotone = 0;
   e->monotone_cfg = e->P.monotone;
   if (int rc = e->fit_lut.ensure(kFitLutBytes)) return bail(rc);
   if (hipMemsetAsync(e->fit_lut.p, 0, kFitLutBytes, e->stream) != hipSuccess) return bail(fail(KG_E_DEVICE, "hipMemset"));
@@ -6223,16 +6283,19 @@ static int schedule_staged_impl(kg_engine* e, int64_t first, int64_t count, kg_s
   // (ABI 13) GPU-holding reservations: the per-pod pass (the batched rounds keep no DeviceShare restore)
   // (ABI 15) reservations holding cpusets: the per-pod pass too (the batched rounds compile the preferred-cpu path out)
   // (ABI 17) RDMA / FPGA requests: the per-pod pass (the batched rounds and the round engine carry the GPU type only)
+  // bal_rounds (Fit + LoadAware + BalancedAllocation on one rank): calls of more than kExactSmall pods leave the exact
+  // pass for the round engine; everything below that asks "does this call run the exact pass" reads exact_call
+  const bool exact_call = e->exact_on && !(e->bal_rounds && count > kExactSmall);
   if (e->dsx_q && count > 0) {
     if (e->rsv_on && e->rgpu_nodes > 0)
       return fail(KG_E_UNSUPPORTED, "RDMA / FPGA requests with reservations that hold GPUs keep the Go path");
     if (!e->exact_on && e->n_ranks > 1)
       return fail(KG_E_UNSUPPORTED, "RDMA / FPGA requests on a multi-rank round-engine profile keep the Go path");
   }
-  if (e->exact_on && e->xr_on && !e->grp_on && !e->rsv_ext_q && !e->dsx_q && e->rgpu_nodes == 0 &&
+  if (exact_call && e->xr_on && !e->grp_on && !e->rsv_ext_q && !e->dsx_q && e->rgpu_nodes == 0 &&
       e->rcpu_nodes == 0 && count >= kXrMin && e->n_nodes > 0)
     return run_xr(e, first, count, stats, t0);
-  if (e->exact_on || e->dsx_q || (count <= kExactSmall && e->n_ranks == 1)) return run_rsv(e, first, count, stats, t0);
+  if (exact_call || e->dsx_q || (count <= kExactSmall && e->n_ranks == 1)) return run_rsv(e, first, count, stats, t0);
   RoundGeom g;
   if (int rc = prepare_rounds(e, g)) return rc;
   const int64_t end = first + count;
@@ -6684,7 +6747,7 @@ static int bench_rsv(kg_engine* e, int which, int iters, double* avg_ms, double*
 }
 
 int kg_bench_kernel(kg_engine* e, int which, int iters, double* avg_ms, double* algo_bytes) {
-  if (e && e->exact_on) return bench_rsv(e, which, iters, avg_ms, algo_bytes);
+  if (e && e->exact_on && !e->bal_rounds) return bench_rsv(e, which, iters, avg_ms, algo_bytes);
   if (!e || iters <= 0 || which < 0 || which > (e && e->ds_on ? 4 : 2)) return fail(KG_E_INVALID, "bad argument");
   if (e->n_staged <= 0) return fail(KG_E_INVALID, "stage a pod queue first");
   RoundGeom g;
@@ -6812,8 +6875,8 @@ int kg_debug_eval_paths(kg_engine* e, int64_t* mismatches) {
 int kg_debug_round_records(kg_engine* e, int64_t first, int64_t nb, int64_t* out_geom, uint64_t* out_lists,
                            int64_t lists_cap_words, uint64_t* out_records) {
   if (!e || !out_geom || !out_lists || !out_records) return fail(KG_E_INVALID, "null argument");
-  if (e->numa_on || e->ds_on || e->exact_on || e->n_ranks > 1)
-    return fail(KG_E_UNSUPPORTED, "the Fit + LoadAware round engine on one rank only");
+  if (e->numa_on || e->ds_on || (e->exact_on && !e->bal_rounds) || e->n_ranks > 1)
+    return fail(KG_E_UNSUPPORTED, "the Fit + LoadAware (+ BalancedAllocation) round engine on one rank only");
   RoundGeom g;
   if (int rc = prepare_rounds(e, g)) return rc;
   if (first < 0 || nb < 1 || nb > g.B || first + nb > e->n_staged)
@@ -6902,8 +6965,8 @@ int kg_debug_resolve(kg_engine* e, int64_t first, int64_t nb, int64_t n_prev, co
                      const int32_t* prev_pods, const int32_t* prev_nodes, int64_t flags, int64_t cursor,
                      int64_t* out_info, uint64_t* out_records, uint64_t* out_keys, int32_t* out_list) {
   if (!e || !out_info || !out_records || !out_keys || !out_list) return fail(KG_E_INVALID, "null argument");
-  if (e->numa_on || e->ds_on || e->exact_on || e->n_ranks > 1)
-    return fail(KG_E_UNSUPPORTED, "the Fit + LoadAware round engine on one rank only");
+  if (e->numa_on || e->ds_on || (e->exact_on && !e->bal_rounds) || e->n_ranks > 1)
+    return fail(KG_E_UNSUPPORTED, "the Fit + LoadAware (+ BalancedAllocation) round engine on one rank only");
   RoundGeom g;
   if (int rc = prepare_rounds(e, g)) return rc;
   if (first < 0 || nb < 1 || nb > g.B || first + nb > e->n_staged)
@@ -7083,6 +7146,27 @@ int kg_debug_fast_mrs(kg_engine* e, const int64_t* req, const int64_t* cap, int6
   HIP_TRY(hipMemcpyAsync(out_ref, b.p + 2 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(out_cpu, b.p + 3 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(out_mem, b.p + 4 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  b.release();
+  return 0;
+}
+
+int kg_debug_balanced(kg_engine* e, const int64_t* alloc, const int64_t* req, const int64_t* pod, int64_t resources,
+                      int64_t* out_ref, int64_t* out_hot, int64_t n) {
+  if (!e || n < 0 || (resources & ~3ll) || (n > 0 && (!alloc || !req || !pod || !out_ref || !out_hot)))
+    return fail(KG_E_INVALID, "bad argument");
+  if (n == 0) return 0;
+  DevBuf<int64_t> b;
+  if (int rc = b.ensure(8 * n)) return rc;
+  HIP_TRY(hipMemcpyAsync(b.p, alloc, 2 * n * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b.p + 2 * n, req, 2 * n * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(b.p + 4 * n, pod, 2 * n * 8, hipMemcpyHostToDevice, e->stream));
+  const int32_t bal = kBalOn | (resources & 1 ? kBalCpu : 0) | (resources & 2 ? kBalMem : 0);
+  debug_balanced<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(b.p, b.p + 2 * n, b.p + 4 * n, bal, b.p + 6 * n,
+                                                                     b.p + 7 * n, n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_ref, b.p + 6 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(out_hot, b.p + 7 * n, n * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   b.release();
   return 0;

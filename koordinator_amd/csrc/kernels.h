@@ -9,6 +9,8 @@
 //     (or MostAllocated, kg_config.fit_scoring_strategy: upstream's mostResourceScorer, DESIGN.md §3.24;
 //      or RequestedToCapacityRatio, kg_fit_shape_set: upstream's broken-linear shape)
 //   LoadAwareScheduling.Score                             — load_aware.go:269-335, scorer :378-397
+//   upstream NodeResourcesBalancedAllocation.Score (only where the caller asks for it: the round engine's PF_BAL
+//     profiles; the exact pass adds the term itself, rsv_dev.h) — defaults_dev.h::balanced_score
 //   weighted sum over plugins                             — upstream RunScorePlugins (framework_extender.go:236-258)
 // eval_fast<PF>() is the same function on hoisted per-node terms, specialised at compile time on the profile
 // (PF bits) and branch-free in the pod flags; the two are checked equal on the device (kg_debug_eval_paths).
@@ -88,6 +90,13 @@ constexpr int PF_FIT_MOST = 32;
 constexpr int PF_FIT_RTCR = 64;
 // eval_node's strategy parameter of a profile: 0 LeastAllocated, 1 MostAllocated, 2 RequestedToCapacityRatio
 constexpr int fit_strategy_of(int pf) { return (pf & PF_FIT_RTCR) ? 2 : (pf & PF_FIT_MOST) ? 1 : 0; }
+// NodeResourcesBalancedAllocation Score on the round engine (legal with every LeastAllocated profile 0..15, the one
+// without PF_FIT_SCORE included; never with PF_FIT_MOST / PF_FIT_RTCR / PF_LA_PROD): the key gains w_bal · balanced_score.
+// An assume can raise the winner's key, so the resolver takes PF_FIT_MOST's rule
+constexpr int PF_BAL = 128;
+// EvalParams.bal: the plugin's weight (≤ 10⁶ < 2²⁰), its two Resources bits and an "on" bit; 0 = the profile does not
+// score NodeResourcesBalancedAllocation on the round engine
+constexpr int32_t kBalWeightMask = (1 << 20) - 1, kBalCpu = 1 << 20, kBalMem = 1 << 21, kBalOn = 1 << 22;
 constexpr int kFitLutBytes = 128;  // the shape table lut[0..100] as uint8_t, zero-padded to 128 bytes (device and LDS)
 
 // node flags (device)
@@ -164,7 +173,7 @@ struct EvalParams {
   int32_t la_prod_score;  // LoadAwareSchedulingArgs.ScoreAccordingProdUsage
   int32_t fit_most;       // NodeResourcesFitArgs.ScoringStrategy.Type == MostAllocated (kg_config.fit_scoring_strategy)
   int32_t fit_rtcr;       // ... == RequestedToCapacityRatio (kg_fit_shape_set; never together with fit_most)
-  int32_t pad4;
+  int32_t bal;            // NodeResourcesBalancedAllocation on the round engine: kBalOn | kBalCpu | kBalMem | weight, or 0
   const uint8_t* fit_lut;  // the shape table in device memory: kFitLutBytes bytes at an address fixed at create
 };
 static_assert(sizeof(EvalParams) == 128, "EvalParams layout (a graph signature hashes its bytes: no implicit padding)");
@@ -260,6 +269,10 @@ __device__ __forceinline__ int64_t div_small(int64_t s, int64_t w) {
   return s / w;
 }
 
+}  // namespace kg
+#include "defaults_dev.h"  // balanced_score for eval_node (the header uses div_small above)
+namespace kg {
+
 // Reference-shaped fused Filter + Score of one node for one pod (runtime profile).  Returns false when any
 // enabled Filter rejects the node; otherwise writes the weighted total Σ_p weight_p · score_p.
 // MOST: the NodeResourcesFit strategy where the caller knows it at compile time (1 = MostAllocated, 0 = LeastAllocated:
@@ -271,7 +284,16 @@ __device__ __forceinline__ int64_t div_small(int64_t s, int64_t w) {
 // s ≤ 100·ws and ws ≤ 2·10⁶ that is (2s + ws) / (2ws) truncating: s/ws is a multiple of 1/ws, so a quotient that is not
 // an exact half lies at least 1/(2ws) ≥ 2.5·10⁻⁷ from one, while the f64 quotient of two exact integers is off by at
 // most 100.5 · 2⁻⁵³ ≈ 1.1·10⁻¹⁴; an exact half is exact in f64 and rounds away from zero, as (2s + ws) / (2ws) does.
-template <int MOST = -1>
+// BAL: 1 = add NodeResourcesBalancedAllocation's term w_bal · balanced_score(Allocatable, Requested, the pod's plain
+// requests) when P.bal says the profile scores it (the round engine's PF_BAL kernels and the debug hooks); 0 = never
+// (the exact pass adds the term from its own DefParams, and must not get it twice).
+__device__ __forceinline__ int64_t balanced_term(const Row& n, const DevPod& p, int32_t bal) {
+  DefParams F{};
+  F.bal_cpu = (bal & kBalCpu) != 0, F.bal_mem = (bal & kBalMem) != 0;
+  return (int64_t)(bal & kBalWeightMask) *
+         balanced_score(n.alloc_cpu, n.alloc_mem, n.req_cpu, n.req_mem, p.req_cpu, p.req_mem, F);
+}
+template <int MOST = -1, int BAL = 0>
 __device__ __forceinline__ bool eval_node(const Row& n, const DevPod& p, const EvalParams& P, int64_t& total,
                                           uint32_t* reject = nullptr, int64_t* fit_out = nullptr,
                                           int64_t* la_out = nullptr) {
@@ -332,6 +354,9 @@ __device__ __forceinline__ bool eval_node(const Row& n, const DevPod& p, const E
       ls = div_small(s, P.la_wsum);
     }
     if (P.la_score) t += ls * P.weight_la;
+  }
+  if constexpr (BAL != 0) {
+    if (P.bal) t += balanced_term(n, p, P.bal);
   }
   if (fit_out) *fit_out = fs;
   if (la_out) *la_out = ls;
@@ -442,6 +467,9 @@ __device__ __forceinline__ bool mem_dom(int64_t cap, int64_t fr) {
 }
 
 // F_RARE for the free terms the profile scores (a pure function of the row; recomputed after each assume).
+// BAL: NodeResourcesBalancedAllocation's domain where the caller knows the profile at compile time (0 = not scored: the
+// kernels specialised on a profile without PF_BAL compile to what they were; 1 = scored), -1 = P.bal at run time.
+template <int BAL = -1>
 __device__ __forceinline__ uint32_t rare_bit(const EvalRow& e, const EvalParams& P) {
   bool ok = true;
   if (P.fit_score) {
@@ -454,9 +482,15 @@ __device__ __forceinline__ uint32_t rare_bit(const EvalRow& e, const EvalParams&
       ok &= mem_dom((int64_t)e.la_alloc_mem, (int64_t)e.la_free_mem) &&
             mem_dom((int64_t)e.la_alloc_mem, (int64_t)e.la_pfree_mem);
   }
+  // NodeResourcesBalancedAllocation (balanced_hot): the Requested free terms of the resources in its Resources list
+  if constexpr (BAL != 0) {
+    if (P.bal & kBalCpu) ok &= cpu_dom(e.alloc_cpu, e.free_cpu);
+    if (P.bal & kBalMem) ok &= mem_dom((int64_t)e.alloc_mem, e.free_mem);
+  }
   return ok ? 0u : F_RARE;
 }
 
+template <int BAL = -1>
 __device__ __forceinline__ EvalRow make_eval_row(const Row& r, const EvalParams& P) {
   EvalRow e;
   e.free_cpu = r.alloc_cpu - r.req_cpu;
@@ -483,7 +517,7 @@ __device__ __forceinline__ EvalRow make_eval_row(const Row& r, const EvalParams&
   e.flags = r.flags;
   e.pad = 0;
   // the f64 memory terms are exact only inside the domain; outside it the exact path re-reads the table
-  e.flags |= rare_bit(e, P);
+  e.flags |= rare_bit<BAL>(e, P);
   return e;
 }
 
@@ -574,6 +608,25 @@ __device__ __forceinline__ int32_t fit_rtcr_score(const uint8_t* lut, int32_t uc
   return ws ? f : 0;
 }
 
+// NodeResourcesBalancedAllocation on the fast paths (PF_BAL): balanced_score on hoisted terms.  rq_* = Requested =
+// capacity − free and the pod's clamped plain request, each an exact integer in f64.  Domain: cpu_dom(capacity, free) /
+// mem_dom(capacity, free) on the Requested free term of every resource in the Resources list, so
+//   - capacity > 0: "allocatable = 0 drops the resource" never happens here, and two configured resources mean n = 2;
+//   - 0 ≤ Requested < 2^30 + 2^24 (cpu), < 2^52 + 2^45 (memory): exact in f64, and Requested + request — below 2^54 — is
+//     the one correctly rounded f64 addition of two exact integers, the same value as float64(Requested + podRequest);
+//   - a clamped request (req_cpu32 = 2^30 + 1 > 2^24 > capacity, req_mem_d = 2^53 > 2^45 > capacity) gives, like the
+//     true one, a fraction > 1, which caps to 1.
+// The quotients are the plain f64 `/` (correctly rounded: no fast-math, no reciprocal shortcut), and the remaining
+// expression is balanced_score's, operation for operation.
+__device__ __forceinline__ int32_t balanced_hot(double rq_cpu, double cap_cpu, double pod_cpu, double rq_mem,
+                                                double cap_mem, double pod_mem, int32_t bal) {
+  if ((bal & (kBalCpu | kBalMem)) != (kBalCpu | kBalMem)) return 100;  // fewer than two resources: std = 0
+  const double xc = (rq_cpu + pod_cpu) / cap_cpu, xm = (rq_mem + pod_mem) / cap_mem;
+  const double fc = xc > 1.0 ? 1.0 : xc, fm = xm > 1.0 ? 1.0 : xm;
+  const double std = fabs((fc - fm) / 2.0);
+  return (int32_t)((1.0 - std) * 100.0);
+}
+
 // Value selects the optimiser cannot turn into a select of field ADDRESSES: that rewrite (select of two loads
 // → load of a selected address) would keep a whole EvalRow array in scratch memory instead of registers.
 __device__ __forceinline__ int64_t pick(bool c, int64_t a, int64_t b) {
@@ -607,7 +660,7 @@ __device__ __forceinline__ bool eval_fast(const EvalRow& n, const DevPod& p, con
     ok = ok & (((pf & P_DAEMONSET) != 0) | ((n.flags & passbit) != 0));
   }
   uint32_t t = 0;
-  if constexpr ((PF & (PF_FIT_SCORE | PF_LA_SCORE)) != 0) rare |= (n.flags & F_RARE) != 0;
+  if constexpr ((PF & (PF_FIT_SCORE | PF_LA_SCORE | PF_BAL)) != 0) rare |= (n.flags & F_RARE) != 0;
   if constexpr ((PF & PF_FIT_RTCR) != 0) {
     // a row inside the domain has allocatable > 0 for every weighted resource; any other is rare and re-evaluated
     const int32_t uc = mrs_cpu((int32_t)n.fnz_cpu - p.nz_cpu32, (int32_t)n.alloc_cpu, n.inv_cpu);
@@ -637,6 +690,11 @@ __device__ __forceinline__ bool eval_fast(const EvalRow& n, const DevPod& p, con
                                 __umul24((uint32_t)qm, (uint32_t)P.la_w_mem));
     const int32_t l = div_est(s, (int32_t)P.la_wsum, P.inv_la_wsum);
     t += __umul24((uint32_t)((n.flags & F_LA_SCORE) ? l : 0), (uint32_t)P.weight_la);
+  }
+  if constexpr ((PF & PF_BAL) != 0) {
+    const int32_t b = balanced_hot((double)(n.alloc_cpu - n.free_cpu), (double)n.alloc_cpu, (double)p.req_cpu32,
+                                   n.alloc_mem - (double)n.free_mem, n.alloc_mem, p.req_mem_d, P.bal);
+    t += __umul24((uint32_t)b, (uint32_t)(P.bal & kBalWeightMask));
   }
   total = t;
   return ok;
@@ -742,6 +800,10 @@ __device__ __forceinline__ HotRow hot_from_cols(const HotCols& c, const EvalPara
       if (P.la_w_mem) ok &= mem_dom(lam, lfm) && (!kProd || mem_dom(lam, lpm));
     }
   }
+  if constexpr ((PF & PF_BAL) != 0) {  // balanced_hot's domain: the Requested free terms
+    if (P.bal & kBalCpu) ok &= cpu_dom(ac, fc);
+    if (P.bal & kBalMem) ok &= mem_dom(am, fm);
+  }
   h.free_cpu = (int32_t)fc;
   h.fnz_cpu = (int32_t)fnc;
   h.alloc_cpu = (int32_t)ac;
@@ -822,6 +884,12 @@ __device__ __forceinline__ bool eval_hot(const HotRow& n, const DevPod& p, const
                                 __umul24((uint32_t)qm, (uint32_t)P.la_w_mem));
     const int32_t l = div_est(s, (int32_t)P.la_wsum, P.inv_la_wsum);
     t += __umul24((uint32_t)((n.flags & F_LA_SCORE) ? l : 0), (uint32_t)P.weight_la);
+  }
+  if constexpr ((PF & PF_BAL) != 0) {
+    // Requested = capacity − free from the terms the row already holds (no new column, HotRow does not grow)
+    const int32_t b = balanced_hot((double)(n.alloc_cpu - n.free_cpu), (double)n.alloc_cpu, (double)p.req_cpu32,
+                                   n.alloc_mem - n.free_mem, n.alloc_mem, p.req_mem_d, P.bal);
+    t += __umul24((uint32_t)b, (uint32_t)(P.bal & kBalWeightMask));
   }
   total = t;
   return ok;

@@ -790,6 +790,20 @@ class Engine:
                                                     len(requested)))
         return ref, oc, om
 
+    def debug_balanced(self, alloc, requested, pod, resources=3):
+        """NodeResourcesBalancedAllocation's score of n (Allocatable, Requested, pod request) triples, each argument an
+        (n, 2) array of (cpu, memory): (reference-shaped, round engine's hoisted form); the second gives -1 outside its
+        exact domain."""
+        cols = [np.ascontiguousarray(np.asarray(a, dtype=np.int64).reshape(-1, 2).T) for a in (alloc, requested, pod)]
+        n = cols[0].shape[1]
+        if any(c.shape[1] != n for c in cols):
+            raise ValueError("alloc, requested and pod must hold the same number of (cpu, memory) pairs")
+        ref = np.zeros(n, dtype=np.int64)
+        hot = np.zeros(n, dtype=np.int64)
+        check(self.lib, self.lib.kg_debug_balanced(self.h, ptr(cols[0]), ptr(cols[1]), ptr(cols[2]), int(resources),
+                                                   ptr(ref), ptr(hot), n))
+        return ref, hot
+
     def debug_fast_mrs(self, requested, capacity):
         """(reference-shaped, cpu-routine, memory-routine) mostRequestedScore; a fast routine gives -1 outside its domain."""
         requested = np.ascontiguousarray(requested, dtype=np.int64)
