@@ -3953,6 +3953,11 @@ int decode_node_numa(const kg_node_numa& n, NumaStatic& s, NumaMut& m) {
     if (cpus > KG_MAX_CPUS || n.sockets > 8 || n.sockets * n.nodes_per_socket > 8)
       return fail(KG_E_UNSUPPORTED, "cpu topology beyond %d cpus / 8 NUMA nodes", KG_MAX_CPUS);
     if (n.cpus_per_core > 2) return fail(KG_E_UNSUPPORTED, "cpus_per_core %lld > 2", (long long)n.cpus_per_core);
+    // the view counts cpus per NUMA node for KG_MAX_NUMA topology nodes: zones on a wider topology (necessarily fewer
+    // zones than it has NUMA nodes) would be scored and split over the first of them only
+    if (n.num_numa > 0 && n.sockets * n.nodes_per_socket > KG_MAX_NUMA)
+      return fail(KG_E_UNSUPPORTED, "%lld NUMA zones on a topology of %lld NUMA nodes (> %d): report none",
+                  (long long)n.num_numa, (long long)(n.sockets * n.nodes_per_socket), KG_MAX_NUMA);
     s.sockets = (int32_t)n.sockets;
     s.nps = (int32_t)n.nodes_per_socket;
     s.cpn = (int32_t)n.cores_per_node;

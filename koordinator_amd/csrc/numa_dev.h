@@ -573,6 +573,9 @@ struct NumaView {
   int32_t cnt[3][kNumaMax];  // [kind: 0 raw, 1 full cores, 2 one per core][NUMA node]
   int32_t tot[3];
   int64_t numa_cpu[kNumaMax], numa_mem[kNumaMax], alloc_cpu[kNumaMax], alloc_mem[kNumaMax];
+  // whole-free-core cpus per socket, one byte each (socket s in bits 8s..8s+7); 0 unless the node has three or more
+  // sockets of 2-cpu cores, the only shape on which odd_full_take can succeed (then a socket holds <= 85 cpus)
+  uint64_t sock_full;
 };
 
 // which count a cpu-bind policy reads (filterCPUsByRequiredCPUBindPolicy only reduces for FullPCPUs / Spread)
@@ -617,6 +620,12 @@ __device__ __forceinline__ NumaView make_view(const NumaStatic* __restrict__ s, 
   v.tot[0] = cs_count(avail);
   v.tot[1] = cs_count(full);
   v.tot[2] = cs_count(spread);
+  v.sock_full = 0;
+  if (t.sockets >= 3 && t.cpc == 2) {
+#pragma unroll
+    for (int sk = 0; sk < 8; ++sk)
+      if (sk < t.sockets) v.sock_full |= (uint64_t)cs_count(cs_and(full, t.socket_cpus(sk))) << (8 * sk);
+  }
   int32_t acnt[kNumaMax];  // allocated cpus per NUMA node
   const int pn = t.per_node();
   if (pn > 0 && (pn & 63) == 0) {
@@ -931,9 +940,41 @@ __device__ __forceinline__ bool alloc_by_hint(const NumaView& v, const NumaPod& 
   return !((key_c && rq_c != 0) || (key_m && rq_m != 0));
 }
 
+// An odd request under a required FullPCPUs policy on 2-cpu cores, taken once over the node (no hint, so
+// allocateCPUSet does not compare the size, resource_manager.go:333-357), from whole free cores only: does takeCPUs
+// return whole cores?  Only by taking one cpu more (cpu_accumulator.go:136-176).  If a socket (so perhaps a NUMA node)
+// holds the request, the per-node / per-socket lists give exactly `needed` cpus: a split core.  Otherwise sockets are
+// taken whole, most free cores first, while the rest still covers one; the others stay "unsatisfied".  If at least a
+// core is still needed (an odd rest: >= 3), the unsatisfied sockets are walked fewest first, core by core: the first
+// one's loop stops with one cpu needed, and the outer loop takes a whole core of the next — if there is a next.  Every
+// other way ends on a single cpu of a core (freeCPUs) or short.  sf: NumaView::sock_full.
+__device__ __forceinline__ bool odd_full_take(uint64_t sf, int needed) {
+  if (sf == 0) return false;
+  int r = needed, unsat = 0;
+#pragma unroll 1
+  for (int it = 0; it < 8; ++it) {
+    int best = 0, bi = 0;
+#pragma unroll
+    for (int sk = 0; sk < 8; ++sk) {
+      const int c = (int)((sf >> (8 * sk)) & 0xFFull);
+      if (c > best) {
+        best = c;
+        bi = sk;
+      }
+    }
+    if (best == 0) break;
+    if (it == 0 && best >= needed) return false;
+    sf &= ~(0xFFull << (8 * bi));
+    if (r >= best) r -= best;
+    else ++unsat;
+  }
+  return r >= 2 && unsat >= 2;
+}
+
 // resourceManager.Allocate feasibility (resource_manager.go:171-360) from counts: the per-NUMA takes of
 // allocateCPUSet never fail, and a FullPCPUs take of k cpus from whole-core lists is whole cores iff k is a
-// multiple of cpus-per-core, so satisfiedRequiredCPUBindPolicy reduces to that parity.
+// multiple of cpus-per-core — or, for an odd k taken once over the node, iff takeCPUs ends on a whole core of a
+// further socket (odd_full_take) — so satisfiedRequiredCPUBindPolicy reduces to that.
 __device__ __forceinline__ bool numa_feasible(const NumaView& v, const NumaPod& p, const NumaHint& h, NumaAlloc& a) {
   a.res = 0;
   const int bind = numa_pref_bind(v, p.preferred);
@@ -958,7 +999,8 @@ __device__ __forceinline__ bool numa_feasible(const NumaView& v, const NumaPod& 
     }
     return ok && got == p.needed;
   }
-  return !(whole && p.needed % v.cpc != 0);
+  if (!(whole && p.needed % v.cpc != 0)) return true;
+  return odd_full_take(v.sock_full, p.needed);
 }
 
 __device__ __forceinline__ bool skip_the_node(const NumaPod& p, int policy) {
